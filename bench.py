@@ -16,10 +16,17 @@ on one device) the same native protocol runs with its collectives over gloo
 (qk_comm_init_host), and the line says so; with enough GPUs a communicator
 that cannot be built is an error, never a silent fallback.
 
-    python bench.py [--gpus N --steps K --warmup W --n IDS_PER_GPU --t 32 --bits 32]
+    python bench.py [--gpus N --steps K --warmup W --ids-per-gpu IDS --t 32 --bits 32]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 
-Rank 0 prints ONE JSON line.  Alongside the metric it reports
+Rank 0 prints ONE JSON line.  A plain run does only what the headline needs:
+it fills the ids, warms up, times --steps steps and prints the metric
+(`value`, `ms_per_step`), the HBM roofline of the timed launches and the
+digest of the last step's result; --dump-outputs DIR also writes that result
+(the folded power sums and the count) as DIR/<name>.npy.  Everything below
+that takes runs of its own is behind --full (`valu`, `clock_ghz`, `parity`,
+`decode_parity`, `configs`, `cpu_baseline`).  The line reports
   roofline      the encode kernel's achieved algorithmic HBM bytes/s (4 B per
                 u32 id) over its average launch duration, measured with HIP
                 events on the launch stream, against the 8 TB/s HBM3E peak;
@@ -134,6 +141,23 @@ RECORDED_DIGESTS = {(32, 32, 1_000_000_000, 0x5EED0002): "523499db79543cdf",
 def digest_of(S, count) -> str:
     import hashlib
     return hashlib.sha256((",".join(str(v) for v in S) + f"|{count}").encode()).hexdigest()[:16]
+
+
+def dump_outputs(path, S, count, bits):
+    """--dump-outputs: the result of the last timed step as float64 .npy files
+    under `path`, every value exact: power_sums.npy, the t folded power sums
+    (u32: shape (t,); u64: shape (t, 2), a sum's high and low 32 bits), and
+    count.npy, shape (1,).  Returns the files written."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    if bits == 32:
+        sums = np.array(S, dtype=np.float64)
+    else:
+        sums = np.array([[v >> 32, v & 0xFFFFFFFF] for v in S], dtype=np.float64)
+    files = {"power_sums.npy": sums, "count.npy": np.array([count], dtype=np.float64)}
+    for name, a in files.items():
+        np.save(os.path.join(path, name), a)
+    return sorted(files)
 
 
 def strong_scaling_check(args, comm, ctx, ids, rank, world, dev_index, bits, t):
@@ -672,10 +696,20 @@ def main():
     ap.add_argument("--t", type=int, default=32)
     ap.add_argument("--bits", type=int, default=32, choices=(32, 64))
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=0x5EED0002)
-    ap.add_argument("--cpu-sample", type=float, default=1e8, help="ids for the CPU baseline (0 disables)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also everything that takes runs of its own: the shader-clock probe "
+                         "(clock_ghz, roofline.valu), the N = 1 configs block and CPU baselines, and for N > 1 the "
+                         "strong-scaling and sharded-decode parity passes.  A plain run sets up, warms up, times "
+                         "--steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64): "
+                         "power_sums (the folded power sums; u64: one [high 32 bits, low 32 bits] row per sum, so "
+                         "every value is exact) and count")
+    ap.add_argument("--cpu-sample", type=float, default=1e8,
+                    help="--full: ids for the CPU baseline (0 disables)")
     ap.add_argument("--configs", type=int, default=1,
-                    help="N = 1: after the headline, the untimed self-checked block of the other single-GPU configs "
-                         "(configs[2], configs[4] and its u64 twin, SURVEY 8f flows / packets); 0 skips it")
+                    help="--full, N = 1: after the headline, the untimed self-checked block of the other single-GPU "
+                         "configs (configs[2], configs[4] and its u64 twin, SURVEY 8f flows / packets); 0 skips it")
     ap.add_argument("--grid", type=int, default=0, help="override workgroups per launch")
     ap.add_argument("--knob", action="append", default=[], help="NAME=VALUE measurement knob (qk_ctx_set_knob)")
     ap.add_argument("--comm", action="store_true",
@@ -685,6 +719,8 @@ def main():
                          "protocol with its collectives over gloo (qk_comm_init_host), to rehearse more ranks than "
                          "GPUs; auto: rccl when the node has a GPU per rank, else host")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import numpy as np
     import torch
@@ -785,13 +821,16 @@ def main():
             S, count = skd.fold_partial_sum(part_host, t, bits)
         log(f"encode result: count={count} S[0..3]={S[:3]}")
         digest = digest_of(S, count)
+        dumped = dump_outputs(args.dump_outputs, S, count, bits) if args.dump_outputs else None
 
-    # untimed, after the timed region: this run's shader clock under the
-    # kernel (roofline.valu), and for N > 1 the strong-scaling parity pass and
-    # what RCCL itself reports on every rank
-    clock_ghz = measure_clock(ctx, step, dev_index, kern_avg_ms)
-    if comm is not None:   # drain the probe's steps (the root merges into a throwaway sketch)
-        comm.encode_sharded_wait((sk.PowerSumQuackU32 if bits == 32 else sk.PowerSumQuackU64)(t))
+    # --full, untimed, after the timed region: this run's shader clock under
+    # the kernel (roofline.valu), and for N > 1 the strong-scaling parity pass;
+    # for N > 1 always, what RCCL itself reports on every rank
+    clock_ghz = None
+    if args.full:
+        clock_ghz = measure_clock(ctx, step, dev_index, kern_avg_ms)
+        if comm is not None:   # drain the probe's steps (the root merges into a throwaway sketch)
+            comm.encode_sharded_wait((sk.PowerSumQuackU32 if bits == 32 else sk.PowerSumQuackU64)(t))
     strong = dec = None
     ranks = None
     if world > 1:
@@ -812,8 +851,9 @@ def main():
             if int(bad.item()):
                 return {"error": err or f"failed on {int(bad.item())} other rank(s)"}, False
             return res, True
-        strong, ok = agreed(strong_scaling_check, args, comm, ctx, ids, rank, world, dev_index, bits, t)
-        dec = agreed(decode_check, comm, ctx, ids, n, rank, world, bits)[0] if ok else {"error": "skipped"}
+        if args.full:
+            strong, ok = agreed(strong_scaling_check, args, comm, ctx, ids, rank, world, dev_index, bits, t)
+            dec = agreed(decode_check, comm, ctx, ids, n, rank, world, bits)[0] if ok else {"error": "skipped"}
         info = comm.rccl_info()
         props = torch.cuda.get_device_properties(dev_index)
         mine = {"rank": rank, "local_rank": local, "device": dev_index,
@@ -882,9 +922,12 @@ def main():
     rec = RECORDED_DIGESTS.get((bits, t, n_total, args.seed))
     if rec:
         out["result"]["equals_recorded"] = digest == rec
+    if dumped:
+        out["dumped_outputs"] = dumped
     if world > 1:
-        out["parity"] = strong
-        out["decode_parity"] = dec
+        if args.full:
+            out["parity"] = strong
+            out["decode_parity"] = dec
         out["ranks"] = ranks
         if data_path == "rccl":
             out["rccl"] = {"ranks_reported": sorted({r["rccl_count"] for r in ranks}),
@@ -892,9 +935,9 @@ def main():
                            "devices": [r["rccl_device"] for r in ranks],
                            "user_ranks": [r["rccl_rank"] for r in ranks]}
 
-    if world == 1 and args.configs and bits == 32 and t == 32:
+    if args.full and world == 1 and args.configs and bits == 32 and t == 32:
         out["configs"] = secondary_configs(ctx, dev_index)
-    if world == 1 and args.cpu_sample > 0:
+    if args.full and world == 1 and args.cpu_sample > 0:
         out["cpu_baseline"], out["cpu_baseline_all_cores"] = cpu_baselines(args, bits, t, start, cnt, ids)
     print(json.dumps(out), flush=True)
     if comm is not None and world == 1:

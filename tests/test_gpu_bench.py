@@ -25,7 +25,7 @@ def run(cmd, timeout=600):
 def test_bench_contract_and_sharded_parity():
     n_total, seed, t = 40_000_000, 0x5EED0002, 32
     one = run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--ids-per-gpu", str(n_total),
-               "--cpu-sample", "2e6"])
+               "--cpu-sample", "2e6", "--full"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in one
@@ -46,7 +46,7 @@ def test_bench_contract_and_sharded_parity():
 
     two = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                "--master-addr", "127.0.0.1", "--master-port", "29561", "bench.py", "--gpus", "2", "--steps", "3",
-               "--warmup", "1", "--ids-per-gpu", str(n_total // 2), "--dist-backend", "host"])
+               "--warmup", "1", "--ids-per-gpu", str(n_total // 2), "--dist-backend", "host", "--full"])
     assert two["n_gpus"] == 2 and two["cpu_baseline"] is None
     assert two["config"]["collectives"] == "host" and "rehearsal" in two["config"]["workload"]
     assert two["result"]["digest"] == one["result"]["digest"]
@@ -64,6 +64,26 @@ def test_bench_contract_and_sharded_parity():
     dp = two["decode_parity"]
     assert dp["equals_single_gpu"] is True and dp["drops_recovered"] is True and dp["d"] == 32 and dp["hits"] >= 32
     assert "rccl" not in two                   # host channel: no RCCL communicator to report
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run: the headline's keys, none of the --full legs, and
+    --dump-outputs writes the last step's folded power sums and count
+    (float64, exact) equal to the oracle's."""
+    import numpy as np
+    n_total, seed, t = 2_000_003, 0x5EED0002, 32
+    out = run([sys.executable, "bench.py", "--gpus", "1", "--steps", "4", "--warmup", "1", "--ids-per-gpu",
+               str(n_total), "--dump-outputs", str(tmp_path)])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in out
+    assert out["steps"] == 4 and out["ms_per_step"] > 0 and out["dtype"] == "u32" and out["unit"] == "identifiers/s"
+    assert abs(out["value"] - n_total / (out["ms_per_step"] * 1e-3)) < 1e-6 * out["value"]
+    assert out["roofline"]["kernel_avg_ms"] > 0 and out["roofline"]["valu"] is None
+    assert out["cpu_baseline"] is None and out["clock_ghz"] is None and "configs" not in out
+    assert sorted(os.listdir(tmp_path)) == ["count.npy", "power_sums.npy"] == out["dumped_outputs"]
+    sums, count = np.load(tmp_path / "power_sums.npy"), np.load(tmp_path / "count.npy")
+    assert sums.dtype == np.float64 and sums.shape == (t,) and count.dtype == np.float64 and count.shape == (1,)
+    assert [int(v) for v in sums] == coracle.encode_u32_seed(seed, n_total, t) and int(count[0]) == n_total
 
 
 def test_bench_native_comm_world1_matches():

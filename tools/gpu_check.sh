@@ -26,7 +26,7 @@ for s in $STEPS; do
     smoke) step smoke 300 python3 -u -c "import __graft_entry__ as g; g.smoke()" || exit 3 ;;
     pytest) step pytest 1200 python3 -u -m pytest tests -m gpu -q -x -p no:cacheprovider -rA --timeout 300 --timeout-method thread ${PYTEST_ARGS:-} ${PYTEST_K:+-k "$PYTEST_K"}; rc=$?; ok_or_testfail $rc || exit 3 ;;
     pytestf) step pytestf 1200 python3 -u -m pytest ${PYTEST_FILES:-tests} -m gpu -q -x -p no:cacheprovider -rA --timeout 300 --timeout-method thread ${PYTEST_K:+-k "$PYTEST_K"}; rc=$?; ok_or_testfail $rc || exit 3 ;;
-    bench) step bench 600 python3 -u bench.py ${BENCH_ARGS:-} || exit 3 ;;
+    bench) step bench 600 python3 -u bench.py --full ${BENCH_ARGS:-} || exit 3 ;;
     configsab)  # the same configs with knob settings alternated: CONFIGS_AB="k=v1 k=v2", CONFIGS_ROUNDS rounds
       for r in $(seq ${CONFIGS_ROUNDS:-2}); do
         for kv in ${CONFIGS_AB}; do
@@ -36,10 +36,10 @@ for s in $STEPS; do
     configs) step configs 900 python3 -u tools/bench_configs.py ${CONFIGS_ARGS:-u64 decode host sweep --cpu} || exit 3 ;;
     prof)
       export TMPDIR=/tmp
-      step prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python3 "$ROOT/bench.py" --steps 20 --warmup 1 --cpu-sample 0 || exit 3 ;;
-    dist2) step dist2 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 5 --warmup 1 --ids-per-gpu 2e8 --cpu-sample 0 || exit 3 ;;
-    dist2full) step dist2full 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29535 bench.py --gpus 2 --steps 3 --warmup 1 --cpu-sample 0 || exit 3 ;;
-    dist4full) step dist4full 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29536 bench.py --gpus 4 --steps 3 --warmup 1 --cpu-sample 0 || exit 3 ;;
+      step prof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python3 "$ROOT/bench.py" --full --steps 20 --warmup 1 --cpu-sample 0 || exit 3 ;;
+    dist2) step dist2 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --gpus 2 --steps 5 --warmup 1 --ids-per-gpu 2e8 --cpu-sample 0 || exit 3 ;;
+    dist2full) step dist2full 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29535 bench.py --full --gpus 2 --steps 3 --warmup 1 --cpu-sample 0 || exit 3 ;;
+    dist4full) step dist4full 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29536 bench.py --full --gpus 4 --steps 3 --warmup 1 --cpu-sample 0 || exit 3 ;;
     roots) step roots 300 python3 -u tools/bench_roots.py ${ROOTS_ARGS:-} || exit 3
            step profroots 120 ./tools/prof_roots 32 300 || exit 3 ;;
     abenc) step abenc 600 python3 -u tools/ab_encode.py ${ABENC_ARGS:-} || exit 3 ;;
@@ -49,7 +49,7 @@ for s in $STEPS; do
     profabflows)
       export TMPDIR=/tmp
       step profabflows 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/profabflows" -o run -- python3 "$ROOT/tools/ab_flows.py" ${PROFAB_ARGS:---modes 1 --rounds 2} || exit 3 ;;
-    dist4) step dist4 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29534 bench.py --gpus 4 --steps 3 --warmup 1 --ids-per-gpu 1e8 --cpu-sample 0 || exit 3 ;;
+    dist4) step dist4 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29534 bench.py --full --gpus 4 --steps 3 --warmup 1 --ids-per-gpu 1e8 --cpu-sample 0 || exit 3 ;;
     tune) step tune 600 ./tools/tune_encode ${TUNE_ARGS:-} || exit 3 ;;
     tunebsgs) step tunebsgs 600 ./tools/tune_bsgs ${TUNE_ARGS:-} || exit 3 ;;
     listctr) step listctr 120 rocprofv3 -L || true ;;
@@ -79,7 +79,7 @@ for s in $STEPS; do
       step fig2_host 600 python3 -u tools/run_fig2.py "$OUT/fig2_host" --trials 100 || exit 3
       step fig2_gpu 600 python3 -u tools/run_fig2.py "$OUT/fig2_gpu" --trials 20 --gpu || exit 3 ;;
     dist2rccl)  # two ranks through the native RCCL communicator (on one GPU if that is all there is)
-      NCCL_DEBUG=WARN step dist2rccl 240 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29544 bench.py --gpus 2 --steps 3 --warmup 1 --ids-per-gpu 1e8 --cpu-sample 0 || exit 3 ;;
+      NCCL_DEBUG=WARN step dist2rccl 240 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29544 bench.py --full --gpus 2 --steps 3 --warmup 1 --ids-per-gpu 1e8 --cpu-sample 0 || exit 3 ;;
     passes)  # u32 t > 80: BSGS passes (default) vs the power chain
       step sweep_passes 300 python3 -u tools/bench_configs.py sweep --steps 6 || exit 3
       step sweep_chain 300 python3 -u tools/bench_configs.py sweep --steps 6 --knob u32_passes=0 || exit 3 ;;

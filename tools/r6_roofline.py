@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""Roofline rows of the bench run's kernels (round 6: bench.py's N = 1 run
-now carries every single-GPU config, so one kernel trace and one FETCH_SIZE
-pass of `python bench.py` cover them all; not product code):
+"""Roofline rows of the bench run's kernels (round 6: bench.py --full's N = 1
+run carries every single-GPU config, so one kernel trace and one FETCH_SIZE
+pass of `python bench.py --full` cover them all; not product code):
 
   <dir>/prof/run_kernel_trace.csv     rocprofv3 --kernel-trace (per dispatch)
   <dir>/pmc/run_counter_collection.csv rocprofv3 --pmc FETCH_SIZE
