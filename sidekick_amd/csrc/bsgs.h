@@ -289,8 +289,136 @@ __device__ __forceinline__ uint32_t pow_uniform(uint32_t xn, uint32_t q, MUL mul
     return r;
 }
 
-// powers of one id; returns nonzero if a lazy fold may have wrapped (the
-// caller then recomputes exactly).  OFF: A[a] = x^(base + a*NB).
+// ---- an id's power chain as one statement -----------------------------------
+// The lazy product (field.h mulfold32_min) is three v_mad_u64_u32:
+//     P = y * x            Q = P + 5 Ph            R = P + 5 Qh,   r = Rl
+// Ph, Qh and the r that feeds the next product are halves of 64-bit pairs, and
+// an asm operand cannot name half of a pair, so a statement per product ends
+// with the result in a compiler-chosen pair and hipcc pads one s_nop between
+// it and the next product's statement.  The whole chain is therefore one
+// statement over a fixed window of VGPRs (gfx950 register tuples are 64-bit
+// aligned, so every result sits in the even register of a pair):
+//     v[6:7]              Q, reused by every product
+//     v[8:9]              x^NB (the last baby, A[0]); R is written over P in
+//                         place, so v8 = r and v9 is the dead high word
+//     v[10:11] .. v[26:27] the giants x^(2 NB), x^(3 NB), ... (up to nine)
+//     v[28:29] ..         the babies x^(NB-1) down to x^2: x^2 sits in
+//                         v[22 + 2 NB], so a shorter chain is a suffix of a
+//                         longer one's text
+// (v0 .. v5 are left alone: the kernels' prologues want them, and a window
+// from v2 spilled five dwords more in the headline kernel; from v10 the
+// small-flow kernel of t = 9..12 needed a 65th VGPR.)  An id costs Q plus one
+// pair per product, as the product-by-product form does.  Unlike there, the
+// odd halves are clobbered by the statement, so no value that lives across
+// the loop can sit in one: body_gen makes up for it by keeping no thread
+// index across its loops.  The running minimum of the results (the wrap
+// check) is formed in the dead v9 inside the statement.  All carry-outs go to
+// the clobbered pair s[58:59], which nothing reads.  Within the statement
+// every hazard is a VALU result read by the next VALU, which the hardware
+// interlocks.
+#define QK_LP(D, DH, Y, X)                                                                             \
+    "v_mad_u64_u32 v[" #D ":" #DH "], s[58:59], " Y ", " X ", 0\n\t"                                   \
+    "v_mad_u64_u32 v[6:7], s[58:59], v" #DH ", 5, v[" #D ":" #DH "]\n\t"                               \
+    "v_mad_u64_u32 v[" #D ":" #DH "], s[58:59], v7, 5, v[" #D ":" #DH "]\n\t"
+// babies: x^2 = x * x first, then each by x (operand [id]) down to v[8:9]
+#define QK_BT1 QK_LP(8, 9, "v28", "%[id]")
+#define QK_BT2 QK_LP(28, 29, "v30", "%[id]") QK_BT1
+#define QK_BT3 QK_LP(30, 31, "v32", "%[id]") QK_BT2
+#define QK_BT4 QK_LP(32, 33, "v34", "%[id]") QK_BT3
+#define QK_BT5 QK_LP(34, 35, "v36", "%[id]") QK_BT4
+#define QK_BT6 QK_LP(36, 37, "v38", "%[id]") QK_BT5
+#define QK_BABIES4 QK_LP(30, 31, "%[id]", "%[id]") QK_BT2
+#define QK_BABIES6 QK_LP(34, 35, "%[id]", "%[id]") QK_BT4
+#define QK_BABIES8 QK_LP(38, 39, "%[id]", "%[id]") QK_BT6
+#define QK_BMIN4 "v_min3_u32 v9, v30, v28, v8\n\t"
+#define QK_BMIN6 QK_BMIN4 "v_min3_u32 v9, v9, v34, v32\n\t"
+#define QK_BMIN8 QK_BMIN6 "v_min3_u32 v9, v9, v38, v36\n\t"
+#define QK_BOUT4 "=&{v30}"(B[1]), "=&{v28}"(B[2]), "=&{v8}"(B[3])
+#define QK_BOUT6 "=&{v34}"(B[1]), "=&{v32}"(B[2]), "=&{v30}"(B[3]), "=&{v28}"(B[4]), "=&{v8}"(B[5])
+#define QK_BOUT8                                                                                       \
+    "=&{v38}"(B[1]), "=&{v36}"(B[2]), "=&{v34}"(B[3]), "=&{v32}"(B[4]), "=&{v30}"(B[5]), "=&{v28}"(B[6]), \
+        "=&{v8}"(B[7])
+#define QK_BCLOB4 "v31", "v29"
+#define QK_BCLOB6 QK_BCLOB4, "v35", "v33"
+#define QK_BCLOB8 QK_BCLOB6, "v39", "v37"
+// giants: each by x^NB (v8)
+#define QK_GIANTS0
+#define QK_GIANTS1 QK_LP(10, 11, "v8", "v8")
+#define QK_GIANTS2 QK_GIANTS1 QK_LP(12, 13, "v10", "v8")
+#define QK_GIANTS3 QK_GIANTS2 QK_LP(14, 15, "v12", "v8")
+#define QK_GIANTS4 QK_GIANTS3 QK_LP(16, 17, "v14", "v8")
+#define QK_GIANTS5 QK_GIANTS4 QK_LP(18, 19, "v16", "v8")
+#define QK_GIANTS6 QK_GIANTS5 QK_LP(20, 21, "v18", "v8")
+#define QK_GIANTS7 QK_GIANTS6 QK_LP(22, 23, "v20", "v8")
+#define QK_GIANTS8 QK_GIANTS7 QK_LP(24, 25, "v22", "v8")
+#define QK_GIANTS9 QK_GIANTS8 QK_LP(26, 27, "v24", "v8")
+#define QK_GMIN0
+#define QK_GMIN1 "v_min_u32_e32 v9, v9, v10\n\t"
+#define QK_GMIN2 "v_min3_u32 v9, v9, v10, v12\n\t"
+#define QK_GMIN3 QK_GMIN2 "v_min_u32_e32 v9, v9, v14\n\t"
+#define QK_GMIN4 QK_GMIN2 "v_min3_u32 v9, v9, v14, v16\n\t"
+#define QK_GMIN5 QK_GMIN4 "v_min_u32_e32 v9, v9, v18\n\t"
+#define QK_GMIN6 QK_GMIN4 "v_min3_u32 v9, v9, v18, v20\n\t"
+#define QK_GMIN7 QK_GMIN6 "v_min_u32_e32 v9, v9, v22\n\t"
+#define QK_GMIN8 QK_GMIN6 "v_min3_u32 v9, v9, v22, v24\n\t"
+#define QK_GMIN9 QK_GMIN8 "v_min_u32_e32 v9, v9, v26\n\t"
+#define QK_GOUT0
+#define QK_GOUT1 , "=&{v10}"(G[0])
+#define QK_GOUT2 QK_GOUT1, "=&{v12}"(G[1])
+#define QK_GOUT3 QK_GOUT2, "=&{v14}"(G[2])
+#define QK_GOUT4 QK_GOUT3, "=&{v16}"(G[3])
+#define QK_GOUT5 QK_GOUT4, "=&{v18}"(G[4])
+#define QK_GOUT6 QK_GOUT5, "=&{v20}"(G[5])
+#define QK_GOUT7 QK_GOUT6, "=&{v22}"(G[6])
+#define QK_GOUT8 QK_GOUT7, "=&{v24}"(G[7])
+#define QK_GOUT9 QK_GOUT8, "=&{v26}"(G[8])
+#define QK_GCLOB0
+#define QK_GCLOB1 , "v11"
+#define QK_GCLOB2 QK_GCLOB1, "v13"
+#define QK_GCLOB3 QK_GCLOB2, "v15"
+#define QK_GCLOB4 QK_GCLOB3, "v17"
+#define QK_GCLOB5 QK_GCLOB4, "v19"
+#define QK_GCLOB6 QK_GCLOB5, "v21"
+#define QK_GCLOB7 QK_GCLOB6, "v23"
+#define QK_GCLOB8 QK_GCLOB7, "v25"
+#define QK_GCLOB9 QK_GCLOB8, "v27"
+
+// B[b] = x^(b+1) for b = 1..NB-1 (lazy), G[g] = x^(NB (g+2)) for g < NG;
+// returns the minimum over all of them.  Only the (NB, NG) listed below are
+// fused; any other falls back to a statement per product.
+template <int NB, int NG>
+struct LazyChain {
+    static constexpr bool fused = false;
+};
+#define QK_CHAIN(NB, NG)                                                                               \
+    template <>                                                                                        \
+    struct LazyChain<NB, NG> {                                                                         \
+        static constexpr bool fused = true;                                                            \
+        static __device__ __forceinline__ uint32_t run(uint32_t id, uint32_t (&B)[NB],                 \
+                                                       uint32_t (&G)[NG ? NG : 1]) {                   \
+            uint32_t mn;                                                                               \
+            (void)G;                                                                                   \
+            asm(QK_BABIES##NB QK_GIANTS##NG QK_BMIN##NB QK_GMIN##NG                                    \
+                : "=&{v9}"(mn), QK_BOUT##NB QK_GOUT##NG                                                \
+                : [id] "v"(id)                                                                         \
+                : "v6", "v7", QK_BCLOB##NB QK_GCLOB##NG, "s58", "s59");                                \
+            return mn;                                                                                 \
+        }                                                                                              \
+    };
+#define QK_CHAINS(NB)                                                                                  \
+    QK_CHAIN(NB, 0) QK_CHAIN(NB, 1) QK_CHAIN(NB, 2) QK_CHAIN(NB, 3) QK_CHAIN(NB, 4) QK_CHAIN(NB, 5)    \
+    QK_CHAIN(NB, 6) QK_CHAIN(NB, 7) QK_CHAIN(NB, 8) QK_CHAIN(NB, 9)
+QK_CHAINS(4)
+QK_CHAINS(6)
+QK_CHAINS(8)
+
+// powers of one id; returns a value below WRAP_BELOW if a lazy fold may have
+// wrapped (the caller then recomputes exactly): the minimum of the products
+// where folds are min-tracked.  The comparison is the caller's, so that it can
+// place an instruction between the chain's statement and the v_cmp that reads
+// its result (hipcc pads one s_nop there otherwise).
+// OFF: A[a] = x^(base + a*NB).
+constexpr uint32_t WRAP_BELOW = 25u;
 template <class C>
 __device__ __forceinline__ uint32_t powers(uint32_t id, uint32_t (&B)[C::NB], uint32_t (&A)[C::ROWS],
                                            uint32_t base = 0, uint32_t xb = 0, uint32_t *xnext = nullptr) {
@@ -298,15 +426,20 @@ __device__ __forceinline__ uint32_t powers(uint32_t id, uint32_t (&B)[C::NB], ui
     B[0] = id;
     if constexpr (C::OFF) {
         uint32_t mn = 0xFFFFFFFFu;
+        if constexpr (LazyChain<NB, 0>::fused) {
+            uint32_t G[1];
+            mn = LazyChain<NB, 0>::run(id, B, G);
+        } else {
 #pragma unroll
-        for (int b = 1; b < NB; ++b) B[b] = mulfold32_min(B[b - 1], B[0], mn);
+            for (int b = 1; b < NB; ++b) B[b] = mulfold32_min(B[b - 1], B[0], mn);
+        }
         const uint32_t xn = B[NB - 1];                                   // x^NB (B[b] = x^(b+1))
         if constexpr (C::XC & 1) A[0] = xb;
         else A[0] = pow_uniform(xn, base / NB, [&](uint32_t u, uint32_t v) { return mulfold32_min(u, v, mn); });
 #pragma unroll
         for (int a = 1; a < NA; ++a) A[a] = mulfold32_min(A[a - 1], xn, mn);
         if constexpr ((C::XC & 2) != 0) *xnext = mulfold32_min(A[NA - 1], xn, mn);
-        return mn < 25u;
+        return mn;
     } else if constexpr (C::FOLD == 0) {
         uint32_t wrapped = 0;
 #pragma unroll
@@ -314,8 +447,19 @@ __device__ __forceinline__ uint32_t powers(uint32_t id, uint32_t (&B)[C::NB], ui
         A[0] = B[NB - 1];
 #pragma unroll
         for (int a = 1; a < NA - 1; ++a) A[a] = mulfold32_fast(A[a - 1], A[0], wrapped);
-        return wrapped;
+        return wrapped ? 0u : 0xFFFFFFFFu;
     } else {
+        // giants after x^NB, and the next pass's x^(NB NA) as one more of them
+        constexpr int NG = NA - 2 + ((C::XC & 2) != 0 ? 1 : 0);
+        if constexpr (!C::TREE && LazyChain<NB, NG>::fused) {
+            uint32_t G[NG ? NG : 1];
+            const uint32_t mn = LazyChain<NB, NG>::run(id, B, G);
+            A[0] = B[NB - 1];
+#pragma unroll
+            for (int a = 1; a < NA - 1; ++a) A[a] = G[a - 1];
+            if constexpr ((C::XC & 2) != 0) *xnext = G[NA - 2];
+            return mn;
+        }
         uint32_t mn = 0xFFFFFFFFu;
         if constexpr (C::TREE) {
 #pragma unroll
@@ -332,7 +476,7 @@ __device__ __forceinline__ uint32_t powers(uint32_t id, uint32_t (&B)[C::NB], ui
 #pragma unroll
         for (int a = 1; a < NA - 1; ++a) A[a] = mulfold32_min(A[a - 1], A[0], mn);
         if constexpr ((C::XC & 2) != 0) *xnext = mulfold32_min(A[NA - 2], A[0], mn);   // x^(NB NA)
-        return mn < 25u;
+        return mn;
     }
 }
 template <class C>
@@ -447,11 +591,16 @@ template <class C>
 __device__ __forceinline__ void one(Acc<C::NB, C::NA, C::ROWS> &S, uint32_t id, uint32_t base = 0, uint32_t xb = 0,
                                     uint32_t *xnext = nullptr) {
     uint32_t B[C::NB], A[C::ROWS];
-    const uint32_t w = powers<C>(id, B, A, base, xb, xnext);
+    const uint32_t mn = powers<C>(id, B, A, base, xb, xnext);
+    // the priority change sits between the chain and the wrap check that reads
+    // its minimum, where an s_nop would stand otherwise (the rare redo runs at
+    // the accumulation's priority)
+    prio_enter<C>();
+    if constexpr (C::PRIO != 0) __builtin_amdgcn_sched_barrier(0);
+    const bool w = mn < WRAP_BELOW;
     if (__builtin_expect(__any(w), 0)) {
         if (w) powers_exact<C>(B, A, base, xb, xnext);
     }
-    prio_enter<C>();
     accumulate<C>(S, B, A);
     prio_exit<C>();
 }
@@ -462,8 +611,8 @@ template <class C>
 __device__ __forceinline__ void two(Acc<C::NB, C::NA, C::ROWS> &S, uint32_t id0, uint32_t id1) {
     static_assert(!C::OFF, "pairs: plain passes only");
     uint32_t B0[C::NB], A0[C::ROWS], B1[C::NB], A1[C::ROWS];
-    const uint32_t w0 = powers<C>(id0, B0, A0);
-    const uint32_t w1 = powers<C>(id1, B1, A1);
+    const bool w0 = powers<C>(id0, B0, A0) < WRAP_BELOW;
+    const bool w1 = powers<C>(id1, B1, A1) < WRAP_BELOW;
     if (__builtin_expect(__any(w0 | w1), 0)) {
         if (w0) powers_exact<C>(B0, A0);
         if (w1) powers_exact<C>(B1, A1);
@@ -492,11 +641,14 @@ __device__ __forceinline__ void four(Acc<C::NB, C::NA, C::ROWS> &S, uint4 w, uin
 
 // Lane partials -> wave butterfly -> LDS -> one sum per power for the
 // workgroup: out(m, s) receives power m + 1's sum (< 2^40) in thread m.
+// tid: the thread's index in the workgroup (body_gen passes one rebuilt after
+// its loops, so that threadIdx.x holds no register across them).
 template <class C, class Out>
-__device__ __forceinline__ void finish(const Acc<C::NB, C::NA, C::ROWS> &S, uint32_t T, Out out) {
+__device__ __forceinline__ void finish(const Acc<C::NB, C::NA, C::ROWS> &S, uint32_t T, Out out,
+                                       uint32_t tid = threadIdx.x) {
     constexpr int NB = C::NB, NA = C::NA;
     __shared__ uint64_t sm[WAVES * NB * NA];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = tid & 63, wave = tid >> 6;
 #pragma unroll
     for (int a = 0; a < NA; ++a) {
 #pragma unroll
@@ -522,7 +674,7 @@ __device__ __forceinline__ void finish(const Acc<C::NB, C::NA, C::ROWS> &S, uint
         }
     }
     __syncthreads();
-    for (uint32_t m = threadIdx.x; m < T; m += BLOCK) {
+    for (uint32_t m = tid; m < T; m += BLOCK) {
         uint64_t s = 0;
 #pragma unroll
         for (int w = 0; w < WAVES; ++w) s += sm[w * (NB * NA) + m];
@@ -569,6 +721,15 @@ __device__ __forceinline__ void body_gen(const uint32_t *__restrict__ ids, uint6
     constexpr bool XI = (C::XC & 1) != 0, XO = (C::XC & 2) != 0;
     Acc<C::NB, C::NA, C::ROWS> S;
     clear<C>(S);
+    // The loops below leave two or three VGPRs to values that only the head,
+    // the tail and finish() read.  gtid - threadIdx.x is the same in every
+    // lane (both callers: a workgroup's first thread), so it and the wave's
+    // number wait in SGPRs, and the thread's index is rebuilt from the lane
+    // number after the loops instead of being kept.
+    const uint64_t gbase64 = gtid - threadIdx.x;
+    const uint32_t gb_lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)gbase64);
+    const uint32_t gb_hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(gbase64 >> 32));
+    const uint32_t wave_s = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint64_t h = head < n ? head : n;
     const uint64_t nbody = (n - h) >> 2;
     const uint4 *__restrict__ v = reinterpret_cast<const uint4 *>(ids + h);
@@ -578,8 +739,12 @@ __device__ __forceinline__ void body_gen(const uint32_t *__restrict__ ids, uint6
     const uint4 *__restrict__ p = v + gtid;
     const uint4 *pc = XI ? reinterpret_cast<const uint4 *>(xin + h) + gtid : nullptr;
     uint4 *po = XO ? reinterpret_cast<uint4 *>(xout + h) + gtid : nullptr;
+    // A lane's group number `it` exists (it < iters) iff p < vend at that trip:
+    // the masked trips test the pointer the loop carries anyway, against a
+    // wave-uniform end, so the trip count holds no VGPR across the main loop.
+    const uint4 *const vend = v + nbody;
     uint4 nxt = make_uint4(0, 0, 0, 0), nxc = make_uint4(0, 0, 0, 0), xo = make_uint4(0, 0, 0, 0);
-    if (iters) {
+    if (p < vend) {
         nxt = *p;
         if constexpr (XI) nxc = *pc;
     }
@@ -600,20 +765,24 @@ __device__ __forceinline__ void body_gen(const uint32_t *__restrict__ ids, uint6
     }
     for (; it < tmax; ++it) {
         const uint4 w = nxt, c = nxc;
+        const bool cur = p < vend;
         p += nthr;
         nxt = make_uint4(0, 0, 0, 0);
-        if (it + 1 < iters) nxt = *p;
+        if (p < vend) nxt = *p;
         if constexpr (XI) {
             pc += nthr;
-            if (it + 1 < iters) nxc = *pc;
+            if (p < vend) nxc = *pc;
         }
         four<C>(S, w, base, c, &xo);
         if constexpr (XO) {
-            if (it < iters) *po = xo;
+            if (cur) *po = xo;
             po += nthr;
         }
+        (void)cur;
     }
     const uint64_t tail0 = h + (nbody << 2);
+    const uint32_t tid = wave_s * 64u + __lane_id();
+    gtid = (((uint64_t)gb_hi << 32) | gb_lo) + tid;
     {
         const bool in = gtid < h;
         uint32_t xn = 0;
@@ -627,7 +796,7 @@ __device__ __forceinline__ void body_gen(const uint32_t *__restrict__ ids, uint6
         if (XO && in) xout[tail0 + gtid] = xn;
     }
 
-    finish<C>(S, T, out);
+    finish<C>(S, T, out, tid);
 }
 
 // the headline kernel's form: grid-stride, one partial per (power, block)

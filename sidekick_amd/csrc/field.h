@@ -88,28 +88,56 @@ QK_HD uint32_t mulfold32_fast(uint32_t y, uint32_t x, uint32_t &wrapped) {
     wrapped |= (r < m);
     return r;
 }
+// The remainder straight from the quotient word.  With Q = P + 5 Ph (mod 2^64),
+// Ql = Pl + 5 Ph (mod 2^32) and th = Qh - Ph (mod 2^32, th <= 5), so
+//     r = Ql + 5 th = Pl + 5 Ph + 5 (Qh - Ph) = Pl + 5 Qh   (mod 2^32):
+// the low word of one more multiply-add (Qh, 5, P), with no subtract.  Only
+// that low word is used: the multiply-add's high word and its 64-bit
+// carry-out are dead.  r is the same 32-bit value as tl + 5 th mod 2^32, so
+// everything said about wraps of tl + 5 th holds for it unchanged.
+//
+// mulfold32_exact still forms th, to tell whether the integer sum tl + 5 th
+// (< 2^32 + 25) passed 2^32: m = 5 th <= 25 and r == tl + m (mod 2^32), so the
+// sum wrapped iff r < m (the carry test of a 32-bit add); then the true sum is
+// r + 2^32 == r + 5 (mod p) with r < 25, which cannot wrap again.
 QK_HD uint32_t mulfold32_exact(uint32_t y, uint32_t x) {
     const uint64_t P = (uint64_t)y * x;
     const uint32_t Ph = (uint32_t)(P >> 32);
     const uint64_t Q = P + (uint64_t)Ph * C32;
-    const uint32_t tl = (uint32_t)Q, th = (uint32_t)(Q >> 32) - Ph;
-    const uint32_t m = th * C32;
-    uint32_t r = tl + m;
-    if (r < m) r += C32;  // wrapped past 2^32 == 5 (mod p); then r < 25, no second wrap
+    const uint32_t Qh = (uint32_t)(Q >> 32);
+    const uint32_t m = (Qh - Ph) * C32;
+    uint32_t r = (uint32_t)P + C32 * Qh;
+    if (r < m) r += C32;
     return r;
 }
 
-// The BSGS kernels' lazy product (bsgs.h): the same t = tl + 5 th, then
-// r = tl + 5 th mod 2^32 with no carry handling.  If that add wrapped, the
+// The BSGS kernels' lazy product (bsgs.h): r = tl + 5 th mod 2^32 with no
+// carry handling, computed as Pl + 5 Qh (above).  If tl + 5 th wrapped, the
 // true sum is r + 2^32 with r < 5 th <= 25, so the caller tracks mn = min(r)
 // over an id's products and redoes the id exactly when mn < 25 (probability
 // ~25 / 2^32 per product; a legitimately small r only costs a redo).
+//
+// Device form: hipcc narrows Pl + 5 Qh to a 32-bit multiply and an add, no
+// cheaper than the subtract it replaces, so the second and third multiply-adds
+// are written out.  Q lives in the fixed pair v[6:7] because its high word has
+// to be named (an asm operand cannot name half of a pair); the third writes R
+// over P (destination == src2, as every accumulate does).  The carry-outs go
+// to the clobbered pair s[58:59], which nothing reads.  bsgs.h fuses whole
+// power chains of this product into one statement (LazyChain).
 QK_HD uint32_t mulfold32_min(uint32_t y, uint32_t x, uint32_t &mn) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint64_t R = (uint64_t)y * x;                           // P, then R in place
+    asm("v_mad_u64_u32 v[6:7], s[58:59], %1, 5, %0\n\t"     // Q = P + 5 Ph
+        "v_mad_u64_u32 %0, s[58:59], v7, 5, %0"             // R = P + 5 Qh
+        : "+v"(R)
+        : "v"((uint32_t)(R >> 32))
+        : "v6", "v7", "s58", "s59");
+    const uint32_t r = (uint32_t)R;
+#else
     const uint64_t P = (uint64_t)y * x;
-    const uint32_t Ph = (uint32_t)(P >> 32);
-    const uint64_t Q = P + (uint64_t)Ph * C32;
-    const uint32_t tl = (uint32_t)Q, th = (uint32_t)(Q >> 32) - Ph;
-    const uint32_t r = tl + th * C32;
+    const uint64_t Q = P + (uint64_t)(uint32_t)(P >> 32) * C32;
+    const uint32_t r = (uint32_t)P + C32 * (uint32_t)(Q >> 32);
+#endif
     mn = r < mn ? r : mn;
     return r;
 }

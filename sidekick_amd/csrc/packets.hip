@@ -149,7 +149,7 @@ __global__ __launch_bounds__(PK_BLOCK) void k_pkt_kernel(const uint8_t *__restri
         if constexpr (SH) {   // this record's powers into LDS (read after the barrier below)
             using Pw = typename C::Pw;
             uint32_t B[8], A[Pw::ROWS];   // A[r] = x^(8 (r + 1))
-            const uint32_t w = bsgs::powers<Pw>(cls == 1 ? id : 0u, B, A);
+            const bool w = bsgs::powers<Pw>(cls == 1 ? id : 0u, B, A) < bsgs::WRAP_BELOW;
             if (__builtin_expect(__any(w), 0)) {
                 if (w) bsgs::powers_exact<Pw>(B, A);
             }
