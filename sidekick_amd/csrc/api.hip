@@ -485,7 +485,7 @@ static int root_test_scan_k(qk_ctx *ctx, const T *coeffs, uint32_t d, const T *d
             }
             if (q == hipSuccess) {
                 if (*done == gen) break;
-                QK_HIP_TRY(hipMemsetAsync(ctx->d_small + RT_DONE, 0, (SMALL_DEV_WORDS - RT_DONE) * sizeof(uint64_t), s));
+                QK_HIP_TRY(hipMemsetAsync(ctx->d_small + RT_DONE, 0, RT_DONE_WORDS * sizeof(uint64_t), s));
                 break;
             }
         }
@@ -705,6 +705,7 @@ int qk_ctx_set_knob(qk_ctx *ctx, const char *name, int64_t value) {
     };
     static const K table[] = {
         {"grid_mult", &qk_knobs::grid_mult, 1, 8},
+        {"enc_dyn", &qk_knobs::enc_dyn, 0, 1},
         {"flow_hist", &qk_knobs::flow_hist, 0, 1 << 20},
         {"flow_byslot", &qk_knobs::flow_byslot, 0, 2},
         {"root_test", &qk_knobs::root_test, 0, 2},

@@ -23,6 +23,16 @@
 //
 // Ids are not reduced mod p first: every product below is exact for any
 // 32-bit operand and x == id (mod p) either way.
+//
+// Two loop structures walk the ids with the same per-id code (four / one):
+//   body_gen   static: grid-stride over 16-byte groups, an unmasked main loop
+//              and <= 2 masked trips per wave, head and tail in every
+//              workgroup (the flow, segment and packet kernels, the offset
+//              passes, and the single-pass kernels at enc_dyn = 0)
+//   body_dyn   dynamic: waves claim chunks of DYN_CH x 64 groups from
+//              counters, every claimed trip unmasked; one wave of the launch
+//              walks the ragged rest, the head and the tail (the single-pass
+//              kernels' default, DESIGN.md §3.2 "Grid")
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -808,6 +818,162 @@ __device__ __forceinline__ void body(const uint32_t *__restrict__ ids, uint64_t 
     body_gen<C>(
         ids, n, head, T, (uint64_t)blockIdx.x * BLOCK + threadIdx.x, (uint64_t)gridDim.x * BLOCK,
         [=](uint32_t m, uint64_t s) { partials[(size_t)m * gridDim.x + blockIdx.x] = s; }, base, xin, xout);
+}
+
+// ---- dynamic form: waves claim chunks of ids (DESIGN.md §3.2 "Grid") --------
+// A chunk is DYN_CH consecutive 16-byte groups per lane for the 64 lanes of a
+// wave: group j of chunk c for lane l is v[(c DYN_CH + j) 64 + l], a coalesced
+// 1 KB per wave and load.  A wave takes its chunks from a counter (one of
+// DYN_NCTR, below): lane 0 adds 1 (relaxed, agent scope) and the wave reads the result into SGPRs.  The
+// counter only ever grows; the launch's claims are numbered from a base that
+// the host keeps: every wave ends with exactly one claim past the counter's
+// chunks, so a launch of W waves moves it by those chunks + W.  Nothing is
+// reset and no wave waits for another.
+//
+// A wave claims chunk k+1 before it walks chunk k (the atomic's round trip is
+// then covered by the SIMD's other waves, which are in their own chunks; the
+// result goes straight to SGPRs, so the claim holds no VGPR across an id), and
+// the last trip of a chunk prefetches the first group of the next one.  Every
+// trip over a claimed chunk is the unmasked form: all 64 lanes have a group.
+// What is no whole chunk — the groups past the last one, the unaligned head
+// and the tail — is walked once per launch, by the wave whose claim returns
+// exactly the number of chunks, with body_gen's masked form (lanes without
+// work feed id 0).  A workgroup whose waves claim nothing stores zero partials.
+// Plain single-pass configurations only (no offset pass, no x^base cache).
+#ifndef QK_DYN_CH
+#define QK_DYN_CH 16   // groups per lane and claim (4 096 ids per chunk)
+#endif
+constexpr int DYN_CH = QK_DYN_CH;
+constexpr uint32_t DYN_GROUPS = DYN_CH * 64;   // 16-byte groups per chunk (4 ids each)
+
+// The claim as one statement: lane 0 alone adds 1 to the counter and the
+// returned value goes straight to SGPRs, so no VGPR is held across the chunk
+// (hipcc's own rendering of the atomic keeps a lane index and the returned
+// pair in VGPRs across the loop: 8 more VGPRs, and spills in the headline
+// kernel).  v[6:7] is the power chain's scratch pair and s[58:59] its dead
+// carry pair; the wait also covers the prefetched group.
+__device__ __forceinline__ uint64_t claim_chunk(unsigned long long *ctr, uint64_t cbase) {
+    uint32_t lo, hi;
+    asm volatile("v_mov_b32_e32 v6, 1\n\t"
+                 "v_mov_b32_e32 v7, 0\n\t"
+                 "s_mov_b64 s[58:59], exec\n\t"
+                 "s_mov_b64 exec, 1\n\t"
+                 "global_atomic_add_x2 v[6:7], v7, v[6:7], %[ctr] sc0\n\t"
+                 "s_mov_b64 exec, s[58:59]\n\t"
+                 "s_waitcnt vmcnt(0)\n\t"
+                 "v_readfirstlane_b32 %[lo], v6\n\t"
+                 "v_readfirstlane_b32 %[hi], v7"
+                 : [lo] "=s"(lo), [hi] "=s"(hi)
+                 : [ctr] "s"(ctr)
+                 : "v6", "v7", "s58", "s59", "memory");
+    return (((uint64_t)hi << 32) | lo) - cbase;
+}
+
+// A chunk's groups are read through a buffer resource on the chunk (base and
+// size in SGPRs): the lane's 16-byte slot is the only VGPR an address needs,
+// and the group's number within the chunk is a scalar offset.
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t chunk_rsrc(const char *vb, uint64_t g) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(vb + g * 16u), 0, (int)(DYN_GROUPS * 16u),
+                                             0x00020000);
+}
+__device__ __forceinline__ uint4 chunk_group(__amdgpu_buffer_rsrc_t rs, uint32_t slot, uint32_t j) {
+    const u32x4_t w = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)slot, (int)(j * 1024u), 0);
+    return make_uint4(w.x, w.y, w.z, w.w);
+}
+
+// One counter serves about 8e7 claims per second whoever asks (agent-scope
+// atomics on one address, measured: 12.5 ns per claim at 4.9e5 and at 2.4e5
+// claims per launch), which 4 096-id chunks of a 1e9-id launch exceed.  The
+// chunks are therefore split into DYN_NCTR contiguous regions with a counter
+// each, DYN_CTR_STRIDE words apart.  A wave starts at the counter of its
+// workgroup's number and moves on to the next one when a claim fails, until
+// it has failed once at every counter: each counter moves by its region's
+// chunks + the launch's waves.  The wave whose claim at counter 0 returns
+// exactly that region's length walks the ragged rest at its end.
+constexpr int DYN_NCTR = 8;
+constexpr int DYN_CTR_STRIDE = 544;   // u64 words: 4 KB + 256 B, another channel whatever the interleave
+struct DynArgs {
+    unsigned long long *ctr;      // counter k at ctr[k * DYN_CTR_STRIDE]
+    uint64_t region;              // chunks per region: ceil(nchunks / DYN_NCTR)
+    uint64_t base[DYN_NCTR];      // the counters' values before this launch
+};
+// chunks of region k (host and device)
+__host__ __device__ inline uint64_t dyn_region_len(uint64_t nchunks, uint64_t region, uint32_t k) {
+    const uint64_t lo = (uint64_t)k * region;
+    return lo >= nchunks ? 0 : (nchunks - lo < region ? nchunks - lo : region);
+}
+
+template <class C>
+__device__ __forceinline__ void body_dyn(const uint32_t *__restrict__ ids, uint64_t n, uint32_t head, uint32_t T,
+                                         uint64_t *__restrict__ partials, const DynArgs &da) {
+    static_assert(!C::OFF && C::XC == 0, "dynamic chunks: plain single-pass configurations");
+    Acc<C::NB, C::NA, C::ROWS> S;
+    clear<C>(S);
+    // as body_gen: the wave's number waits in an SGPR and the thread's index
+    // is rebuilt after the loops
+    const uint32_t wave_s = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint64_t h = head < n ? head : n;
+    const uint64_t nbody = (n - h) >> 2;
+    const uint64_t nchunks = nbody / DYN_GROUPS;
+    const char *vb = reinterpret_cast<const char *>(ids + h);
+    const uint32_t slot = __lane_id() * 16u;
+    constexpr uint64_t NONE = ~0ull;
+    // the claim state is wave-uniform (SGPRs)
+    uint32_t k = blockIdx.x % (uint32_t)DYN_NCTR, failed = 0;
+    bool rest_mine = false;
+    auto claim = [&]() -> uint64_t {
+        while (failed < (uint32_t)DYN_NCTR) {
+            const uint64_t idx = claim_chunk(da.ctr + (size_t)k * DYN_CTR_STRIDE, da.base[k]);
+            const uint64_t len = dyn_region_len(nchunks, da.region, k);
+            if (idx < len) return (uint64_t)k * da.region + idx;
+            if (k == 0 && idx == len) rest_mine = true;
+            k = k + 1 == (uint32_t)DYN_NCTR ? 0u : k + 1;
+            ++failed;
+        }
+        return NONE;
+    };
+    uint4 nxt = make_uint4(0, 0, 0, 0);
+    uint64_t cur = claim();
+    __amdgpu_buffer_rsrc_t rs = chunk_rsrc(vb, 0);
+    if (cur != NONE) {
+        rs = chunk_rsrc(vb, cur * DYN_GROUPS);
+        nxt = chunk_group(rs, slot, 0);
+    }
+    while (cur != NONE) {
+        const uint64_t next = claim();
+        for (uint32_t j = 1; j < (uint32_t)DYN_CH; ++j) {
+            const uint4 w = nxt;
+            nxt = chunk_group(rs, slot, j);
+            four<C>(S, w, 0);
+        }
+        const uint4 w = nxt;
+        if (next != NONE) {
+            rs = chunk_rsrc(vb, next * DYN_GROUPS);
+            nxt = chunk_group(rs, slot, 0);
+        }
+        four<C>(S, w, 0);
+        cur = next;
+    }
+    if (rest_mine) {   // one wave of the launch: the ragged rest, masked
+        const uint32_t lane = __lane_id();
+        const uint32_t rest = (uint32_t)(nbody - nchunks * DYN_GROUPS);   // < DYN_GROUPS
+        rs = chunk_rsrc(vb, nchunks * DYN_GROUPS);
+        nxt = make_uint4(0, 0, 0, 0);
+        if (lane < rest) nxt = chunk_group(rs, slot, 0);
+        for (uint32_t j = 0; j * 64u < rest; ++j) {   // <= DYN_CH trips
+            const uint4 w = nxt;
+            nxt = make_uint4(0, 0, 0, 0);
+            if ((j + 1) * 64u + lane < rest) nxt = chunk_group(rs, slot, j + 1);
+            four<C>(S, w, 0);
+        }
+        const uint64_t tail0 = h + (nbody << 2);
+        one<C>(S, lane < h ? ids[lane] : 0u);
+        one<C>(S, lane < n - tail0 ? ids[tail0 + lane] : 0u);
+    }
+    finish<C>(
+        S, T, [=](uint32_t m, uint64_t s) { partials[(size_t)m * gridDim.x + blockIdx.x] = s; },
+        wave_s * 64u + __lane_id());
 }
 
 } // namespace bsgs

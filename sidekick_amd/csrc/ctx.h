@@ -13,7 +13,10 @@
 // removed"); what is left selects between live product paths — the defaults
 // below are the product's own choices — or injects a test fault.
 struct qk_knobs {
-    int grid_mult = 3;     // encode launches: resident workgroups x this (1: one round; grid_for, encode.hip)
+    int grid_mult = 3;     // static encode launches: resident workgroups x this (1: one round; grid_for, encode.hip)
+    int enc_dyn = 1;       // 1: the single-pass u32 BSGS encode's waves claim chunks of ids from counters, one
+                           // resident round (bsgs.h body_dyn); 0: the static grid-stride form (tests compare
+                           // both with the oracle; same-process A/Bs)
     int flow_hist = 32;    // per-flow batches of at most this many flows (and a table of <= 8192 slots) are
                            // grouped by per-workgroup slot histograms instead of the radix sort (0: never);
                            // 16 flows 2.76 vs 2.90 ms, 64: 3.17 vs 3.05, 1000: 5.80 vs 3.68
@@ -62,6 +65,9 @@ struct qk_ctx {
     uint64_t rt_gen = 0;
     uint64_t *d_hits = nullptr;
     size_t hits_cap = 0;
+    // the dynamic encode's chunk counters (d_small[ENC_CLAIM + k * stride])
+    // only grow: their values before the next launch (encode.hip run_encode_dyn)
+    uint64_t enc_claim_base[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
     // per-flow batches (flows.hip): per-packet arena (slots, ids, sort
     // buffers), per-flow arena (segment info, accumulators, work items) and
@@ -145,7 +151,13 @@ constexpr size_t SMALL_KT = SMALL_WORDS - 8;
 // serialises: +15 µs); zeroed at context creation, each reset by its taker
 constexpr uint32_t RT_DONE_GROUPS = 32;
 constexpr size_t RT_DONE = SMALL_WORDS;
-constexpr size_t SMALL_DEV_WORDS = RT_DONE + 16 * (RT_DONE_GROUPS + 1);
+constexpr size_t RT_DONE_WORDS = 16 * (RT_DONE_GROUPS + 1);
+// d_small[ENC_CLAIM ..) (device only): the dynamic encode's 8 chunk counters,
+// 544 words apart (bsgs.h DYN_NCTR, DYN_CTR_STRIDE; encode.hip checks both);
+// zeroed at context creation and never reset
+constexpr size_t ENC_CLAIM = RT_DONE + RT_DONE_WORDS;
+constexpr size_t ENC_CLAIM_WORDS = 8 * 544;
+constexpr size_t SMALL_DEV_WORDS = ENC_CLAIM + ENC_CLAIM_WORDS;
 
 // One no-op kernel per translation unit.  HIP loads a translation unit's code
 // object at the first launch of any of its kernels, and sets up its staging

@@ -14,8 +14,14 @@
 //     4.47 SIMD-cycles of VALU issue per id (the algorithmic anchor,
 //     tools/issue_model.py); the kernel issues 1.19 VALU + 0.76 SALU
 //     wave-instructions per id, each id's MAC phase at raised wave priority
-//     (s_setprio, knob bsgs_prio), over encode grids of three rounds of
-//     resident workgroups (knob grid_mult), and runs at 0.86-0.89 of the
+//     (s_setprio, knob bsgs_prio).  Streams below 2^32 ids take the dynamic
+//     form k_encode_u32_bsgs_dyn (knob enc_dyn): one round of resident
+//     workgroups whose waves claim 4 096-id chunks from eight counters; only
+//     the wave that finds the chunks exhausted at counter 0 runs masked trips
+//     and the head / tail (bsgs.h body_dyn, run_encode_dyn below).  Longer
+//     streams and enc_dyn = 0 take the static grid-stride form over three
+//     rounds of resident workgroups (knob grid_mult; also the u64 kernels,
+//     the chains and, at one round, the passes).  It runs at 0.86-0.89 of the
 //     anchor at the bench run's own shader clock (bench.py roofline.valu,
 //     DESIGN.md §4) and ~0.20-0.21 of the HBM read roofline (4 B/id; the
 //     line moves with the box's shader clock, 2.0-2.1 GHz).
@@ -117,6 +123,16 @@ __global__ __launch_bounds__(BLOCK, (NB * NA == 32 ? 5 : NB * NA > 64 ? 2 : NB *
                                                                                                         T, partials);
 }
 
+// The same with the ids handed out dynamically (bsgs.h body_dyn): the waves
+// claim chunks of 64 x DYN_CH 16-byte groups from the counter `ctr`, whose
+// value before this launch is `cbase`.
+template <int NB, int NA, int SG, int PRIO = 1>
+__global__ __launch_bounds__(BLOCK, (NB * NA == 32 ? 5 : NB * NA > 64 ? 2 : NB * NA > 40 ? 3 : 4)) void k_encode_u32_bsgs_dyn(
+    const uint32_t *__restrict__ ids, uint64_t n, uint32_t head, uint32_t T, uint64_t *__restrict__ partials,
+    const bsgs::DynArgs da) {
+    bsgs::body_dyn<bsgs::Cfg<NB, NA, SG, QK_BSGS_ROW0, QK_BSGS_FOLD, false, false, 0, false, PRIO ? 4 : 0>>(
+        ids, n, head, T, partials, da);
+}
 
 // Pass 0 of a multi-pass encode (powers 1..80) that also writes x^80 per id
 // for pass 1 (the x^base cache, enc32_passes)
@@ -617,10 +633,12 @@ static uint32_t grid_for(qk_ctx *ctx, KernelT kern, uint64_t units, uint32_t per
     if (ctx->grid_override) return ctx->grid_override;
     int occ = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, BLOCK, 0) != hipSuccess || occ < 1) occ = 1;
-    // knob grid_mult: resident workgroups x this.  The encode kernels take
-    // one contiguous run per workgroup; with one round of workgroups the
-    // launch ends with the slowest CU's run, with three the runs are a third
-    // as long and the CUs that finish early take the later ones
+    // knob grid_mult: resident workgroups x this.  The static encode kernels
+    // (the u64 kernels, the chains, the u32 BSGS kernels at enc_dyn = 0 or
+    // n >= 2^32) split the ids evenly over the grid; with one round of
+    // workgroups the launch ends with the slowest CU's share, with three the
+    // shares are a third as long and the CUs that finish early take the
+    // later workgroups (the dynamic form asks for one round: mult = 1)
     // (mult > 0: fixed by the caller — u32 t > 48 and the u32 passes measured
     // 0.4-2.3 % slower at three rounds, profiles/r04/grid_mult/)
     const uint64_t full = (uint64_t)ctx->num_cus * (uint64_t)occ * (uint64_t)(mult > 0 ? mult : ctx->knobs.grid_mult);
@@ -659,6 +677,45 @@ static int run_encode(qk_ctx *ctx, KernelT kern, FinT fin, uint32_t GK, uint32_t
     hipLaunchKernelGGL(kern, dim3(nb), dim3(BLOCK), 0, s, d_ids, (uint64_t)n, head, T, partials);
     prof_end(ctx, s, e0);
     QK_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(fin, dim3(T), dim3(BLOCK), 0, s, partials, nb, T, d_ids, (uint64_t)n, d_partial,
+                       accumulate);
+    QK_HIP_TRY(hipGetLastError());
+    return scratch_release(ctx, s);
+}
+
+// The dynamic form of a single-pass u32 BSGS encode (bsgs.h body_dyn): one
+// round of resident workgroups (or the override) whose waves claim chunks of
+// ids from the counters at d_small[ENC_CLAIM], one per region of the chunks.
+// The counters are never reset: a launch of nb workgroups moves each by its
+// region's chunks + nb * WAVES (every wave ends with one failed claim at
+// every counter), and the context keeps their values for the next launch's
+// bases.  Launches are ordered by the scratch hand-off (scratch_acquire /
+// scratch_release), so a launch finds the counters at its bases whatever
+// stream it runs on.
+static_assert((size_t)bsgs::DYN_NCTR * bsgs::DYN_CTR_STRIDE <= ENC_CLAIM_WORDS &&
+                  bsgs::DYN_NCTR == sizeof(qk_ctx::enc_claim_base) / sizeof(uint64_t),
+              "ctx.h: room for the dynamic encode's counters and their bases");
+template <typename KernelT, typename FinT>
+static int run_encode_dyn(qk_ctx *ctx, KernelT kern, FinT fin, uint32_t GK, const uint32_t *d_ids, size_t n,
+                          uint32_t head, uint32_t T, uint64_t *d_partial, int accumulate, hipStream_t s) {
+    const uint32_t nb = grid_for(ctx, kern, ((uint64_t)n + 3) / 4, BLOCK, 1);
+    int rc = ensure_scratch(ctx, (size_t)nb * GK * sizeof(uint64_t), s);
+    if (rc) return rc;
+    uint64_t *partials = (uint64_t *)ctx->d_scratch;
+    rc = scratch_acquire(ctx, s);
+    if (rc) return rc;
+    const uint64_t h = head < n ? head : n;
+    const uint64_t nchunks = ((n - h) >> 2) / bsgs::DYN_GROUPS;
+    bsgs::DynArgs da;
+    da.ctr = (unsigned long long *)(ctx->d_small + ENC_CLAIM);
+    da.region = (nchunks + bsgs::DYN_NCTR - 1) / bsgs::DYN_NCTR;
+    for (int k = 0; k < bsgs::DYN_NCTR; ++k) da.base[k] = ctx->enc_claim_base[k];
+    hipEvent_t e0 = prof_begin(ctx, s);
+    hipLaunchKernelGGL(kern, dim3(nb), dim3(BLOCK), 0, s, d_ids, (uint64_t)n, head, T, partials, da);
+    prof_end(ctx, s, e0);
+    QK_HIP_TRY(hipGetLastError());
+    for (int k = 0; k < bsgs::DYN_NCTR; ++k)
+        ctx->enc_claim_base[k] += bsgs::dyn_region_len(nchunks, da.region, (uint32_t)k) + (uint64_t)nb * WAVES;
     hipLaunchKernelGGL(fin, dim3(T), dim3(BLOCK), 0, s, partials, nb, T, d_ids, (uint64_t)n, d_partial,
                        accumulate);
     QK_HIP_TRY(hipGetLastError());
@@ -1007,12 +1064,21 @@ static int enc32(qk_ctx *ctx, const uint32_t *ids, size_t n, uint32_t T, uint64_
     // a tiny override grid over a huge n takes the all-VALU form.
     const uint64_t min_grid = ctx->grid_override ? ctx->grid_override : (uint64_t)ctx->num_cus;
     const bool sc_ok = n / (4ull * BLOCK * min_grid) < (1ull << 24) - 2;
-#define QK_BSGS(NB_, NA_, G_)                                                                                 \
+    // Dynamic form (knob enc_dyn): a wave's scalar wrap totals are 32-bit and
+    // its share of the ids is not fixed, so n stays below 2^32 (one wave
+    // alone could take every chunk: < 2^32 wraps per accumulator); longer
+    // streams keep the static split.
+    const bool dyn = ctx->knobs.enc_dyn != 0 && n < (1ull << 32);
+#define QK_BSGS_STATIC(NB_, NA_, G_)                                                                          \
     run_encode<uint32_t>(ctx, k_encode_u32_bsgs<NB_, NA_, G_, 1>, k_finalize_u32, NB_ * NA_, 1, ids, n, head, T, \
                          (n + 3) / 4, BLOCK, out, acc, s, NB_ * NA_ > 48 ? 1 : 0)
+#define QK_BSGS(NB_, NA_, G_)                                                                                 \
+    (dyn ? run_encode_dyn(ctx, k_encode_u32_bsgs_dyn<NB_, NA_, G_, 1>, k_finalize_u32, NB_ * NA_, ids, n, head, T, \
+                          out, acc, s)                                                                        \
+         : QK_BSGS_STATIC(NB_, NA_, G_))
     if (T >= 5 && T <= 8 && sc_ok) return QK_BSGS(4, 2, 1);
-    if (T >= 9 && T <= 12) return sc_ok ? QK_BSGS(4, 3, 3) : QK_BSGS(4, 3, 0);
-    if (T >= 13 && T <= 16) return sc_ok ? QK_BSGS(4, 4, 4) : QK_BSGS(4, 4, 0);
+    if (T >= 9 && T <= 12) return sc_ok ? QK_BSGS(4, 3, 3) : QK_BSGS_STATIC(4, 3, 0);
+    if (T >= 13 && T <= 16) return sc_ok ? QK_BSGS(4, 4, 4) : QK_BSGS_STATIC(4, 4, 0);
     // Round-3 shapes: the (NB, NA) with the fewest issue cycles for the
     // powers actually needed — modmuls NB - 1 + NA - 2 at ~17 cycles, MACs
     // NB (NA - 1) and row-0 adds NB at ~4.2, measured: 17..28
@@ -1037,10 +1103,12 @@ static int enc32(qk_ctx *ctx, const uint32_t *ids, size_t n, uint32_t T, uint64_
     } else {
         // the all-VALU forms that fit the registers; t 33..80 would spill, so
         // a grid too small for scalar counts takes the power chain there
-        if (T >= 17 && T <= 24) return QK_BSGS(6, 4, 0);
-        if (T >= 25 && T <= 32) return QK_BSGS(8, 4, 0);
+        // (static only: !sc_ok needs n >= 2^34, beyond the dynamic form)
+        if (T >= 17 && T <= 24) return QK_BSGS_STATIC(6, 4, 0);
+        if (T >= 25 && T <= 32) return QK_BSGS_STATIC(8, 4, 0);
     }
 #undef QK_BSGS
+#undef QK_BSGS_STATIC
     int G, K;
     choose_gk(T, 32, K32_G1, 10, K32_GN, 4, G, K);
     switch (G) {
