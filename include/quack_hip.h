@@ -325,6 +325,47 @@ int qk_u64_decode_device(qk_ctx *ctx, const qk_u64 *diff, const uint64_t *d_log,
                          int stop_at_last, uint64_t *hits, size_t cap, size_t *n_hits, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Batched per-flow decode: the decode twin of the segmented encode.  A sender
+ * that serves many flows holds one diff quACK per flow (one per AddrKey, what
+ * SidekickMulti emits: sidekick_multi.rs:65-90) and runs media_client.rs:296-313
+ * for each; these two calls do it for nseg flows in one pass.
+ * `diffs` holds nseg consecutive qk_u32 records of qk_u32_size(threshold)
+ * bytes, exactly what qk_u32_encode_flows_device / _segments_device write,
+ * in host memory or in device memory of ctx's GPU.  A record whose threshold
+ * field differs from `threshold` -> QK_E_MISMATCH for the whole call.  All
+ * outputs are host memory; both calls are synchronous on `stream`.
+ * ---------------------------------------------------------------------- */
+/* diff_quack.to_coeffs() (the :304 step of media_client.rs:296-313) for nseg diff
+ * sketches of one threshold (one per flow, sidekick_multi.rs:65-90), Newton's identities on
+ * the device.  coeffs is [nseg][threshold]: row g holds c_1..c_d in its first
+ * degrees[g] entries, bit-equal to qk_u32_to_coeffs on record g, zero after
+ * them.  status[g] is QK_OK, or QK_E_UNDECODABLE when count > threshold (then
+ * degrees[g] == 0; the call itself still returns QK_OK). */
+int qk_u32_to_coeffs_segments_device(qk_ctx *ctx, const uint8_t *diffs, size_t nseg, uint32_t threshold,
+                                     uint32_t *coeffs, uint32_t *degrees, int32_t *status, void *stream);
+/* Log entries per work item of the batched root test: a longer segment is cut
+ * into slices of this many entries, one workgroup each. */
+#define QK_SEG_DECODE_ITEM 2048u
+/* decode_with_log (media_client.rs:296-313) for nseg (diff, log segment)
+ * pairs in one pass — the per-flow quACKs of sidekick_multi.rs:65-90 against
+ * the sender's logs kept grouped by flow: d_log is a device array, segment g
+ * = [offsets[g], offsets[g+1]) with host offsets (nseg + 1, non-decreasing),
+ * as in qk_u32_encode_segments_device.  hits receives positions into d_log,
+ * ascending (segment order, then log order); hit_offsets[nseg + 1] is their
+ * CSR index by segment.  Segment g's slice minus offsets[g] is what
+ * qk_u32_decode_host(diff_g, log + offsets[g], ...) returns: count == 0 -> no
+ * hits, every entry congruent to a root is a hit (duplicates included), and
+ * with stop_at_last the segment is cut at its own first entry equal to
+ * diff_g->last_value (when has_last).  status[g]: QK_OK, or QK_E_UNDECODABLE
+ * (count > threshold: no hits for g; the call still returns QK_OK).
+ * *n_hits = total hits; cap < total -> QK_E_CAPACITY with hit_offsets fully
+ * written.  nseg == 0 -> QK_OK with hit_offsets[0] = 0. */
+int qk_u32_decode_segments_device(qk_ctx *ctx, const uint8_t *diffs, const uint32_t *d_log,
+                                  const uint64_t *offsets, size_t nseg, uint32_t threshold, int stop_at_last,
+                                  uint64_t *hits, size_t cap, uint64_t *hit_offsets, int32_t *status,
+                                  size_t *n_hits, void *stream);
+
+/* ------------------------------------------------------------------------
  * Multi-GPU: the id stream cut into contiguous shards, one
  * per GPU in global rank order, merged with ONE RCCL reduce over xGMI.
  * The reference callers are single processes (sidekick.rs:58-127,

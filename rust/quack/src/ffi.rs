@@ -10,6 +10,10 @@
 
 use std::os::raw::{c_char, c_int, c_void};
 
+/// The header's `int32_t` (per-segment status arrays), under its C name so the
+/// declarations below read like the prototypes.
+pub type int32_t = i32;
+
 pub const QK_P32: u32 = 4_294_967_291;
 pub const QK_P64: u64 = 18_446_744_073_709_551_557;
 pub const QK_MAX_THRESHOLD: u32 = 1024;
@@ -205,6 +209,15 @@ extern "C" {
     pub fn qk_u64_decode_device(ctx: *mut qk_ctx, diff: *const qk_u64, d_log: *const u64, n: usize,
                                 stop_at_last: c_int, hits: *mut u64, cap: usize, n_hits: *mut usize,
                                 stream: *mut c_void) -> c_int;
+
+    // batched per-flow decode
+    pub fn qk_u32_to_coeffs_segments_device(ctx: *mut qk_ctx, diffs: *const u8, nseg: usize, threshold: u32,
+                                            coeffs: *mut u32, degrees: *mut u32, status: *mut int32_t,
+                                            stream: *mut c_void) -> c_int;
+    pub fn qk_u32_decode_segments_device(ctx: *mut qk_ctx, diffs: *const u8, d_log: *const u32,
+                                         offsets: *const u64, nseg: usize, threshold: u32, stop_at_last: c_int,
+                                         hits: *mut u64, cap: usize, hit_offsets: *mut u64, status: *mut int32_t,
+                                         n_hits: *mut usize, stream: *mut c_void) -> c_int;
 
     // multi-GPU over RCCL
     pub fn qk_comm_unique_id(id: *mut u8) -> c_int;

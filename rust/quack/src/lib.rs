@@ -513,6 +513,80 @@ pub unsafe fn encode_flows_device(ctx: &Context, d_bufs: *const u8, n: usize, st
     }
 }
 
+/// The records of a batch of diff sketches of one threshold, back to back as
+/// the batched decode reads them; `QK_E_MISMATCH` when the thresholds differ.
+fn pack_segment_records(diffs: &[PowerSumQuackU32]) -> Result<(Vec<u32>, u32)> {
+    let t = diffs.first().map_or(1, |q| q.threshold());
+    let mut rec = Vec::with_capacity(diffs.len() * (4 + t));
+    for q in diffs {
+        if q.threshold() != t {
+            return Err(QuackError { status: ffi::QK_E_MISMATCH });
+        }
+        rec.extend_from_slice(&q.words);
+    }
+    Ok((rec, t as u32))
+}
+
+/// `to_coeffs` (`media_client.rs:304`) of one diff sketch per flow
+/// (`sidekick_multi.rs:65-90`) in one device pass: the coefficient vector of
+/// every sketch (empty where its status is `QK_E_UNDECODABLE`) and the
+/// per-sketch status.
+pub fn to_coeffs_segments_device(ctx: &Context, diffs: &[PowerSumQuackU32]) -> Result<(Vec<Vec<u32>>, Vec<i32>)> {
+    let (rec, t) = pack_segment_records(diffs)?;
+    let n = diffs.len();
+    let mut coeffs = vec![0u32; n.max(1) * t as usize];
+    let (mut deg, mut status) = (vec![0u32; n.max(1)], vec![0i32; n.max(1)]);
+    check(unsafe {
+        ffi::qk_u32_to_coeffs_segments_device(ctx.raw, rec.as_ptr() as *const u8, n, t, coeffs.as_mut_ptr(),
+                                              deg.as_mut_ptr(), status.as_mut_ptr(), ptr::null_mut())
+    })?;
+    status.truncate(n);
+    let rows = (0..n).map(|g| coeffs[g * t as usize..g * t as usize + deg[g] as usize].to_vec()).collect();
+    Ok((rows, status))
+}
+
+/// Missing positions of a batch of flows (`decode_segments_device`): the
+/// positions into the grouped log, ascending, their CSR index by flow and the
+/// per-flow status (`QK_OK` or `QK_E_UNDECODABLE`).
+pub struct SegmentHits {
+    pub hits: Vec<u64>,
+    pub hit_offsets: Vec<u64>,
+    pub status: Vec<i32>,
+}
+
+/// `decode_with_log` (`media_client.rs:296-313`) for one diff sketch per flow
+/// (`sidekick_multi.rs:65-90`) against the sender's logs grouped by flow, in
+/// one device pass: flow g's log is `d_log[offsets[g]..offsets[g + 1]]`.
+///
+/// # Safety
+/// `d_log` must be device memory of `ctx`'s GPU holding `offsets.last()` ids.
+pub unsafe fn decode_segments_device(ctx: &Context, diffs: &[PowerSumQuackU32], d_log: *const u32, offsets: &[u64],
+                                     stop_at_last: bool, stream: *mut c_void) -> Result<SegmentHits> {
+    let (rec, t) = pack_segment_records(diffs)?;
+    let n = diffs.len();
+    if offsets.len() != n + 1 {
+        return Err(QuackError { status: ffi::QK_E_INVAL });
+    }
+    let mut cap = 1024usize.max(4 * n);
+    loop {
+        let mut hits = vec![0u64; cap];
+        let mut hit_offsets = vec![0u64; n + 1];
+        let mut status = vec![0i32; n.max(1)];
+        let mut nh = 0usize;
+        let rc = ffi::qk_u32_decode_segments_device(ctx.raw, rec.as_ptr() as *const u8, d_log, offsets.as_ptr(), n, t,
+                                                    stop_at_last as c_int, hits.as_mut_ptr(), cap,
+                                                    hit_offsets.as_mut_ptr(), status.as_mut_ptr(), &mut nh, stream);
+        if rc == ffi::QK_E_CAPACITY && nh > cap {
+            cap = nh;
+            continue;
+        }
+        check(rc)?;
+        hits.truncate(nh);
+        status.truncate(n);
+        return Ok(SegmentHits { hits, hit_offsets, status });
+    }
+}
+
 /// Multi-GPU communicator over RCCL (xGMI): one process driving several
 /// GPUs ([`Comm::new`]) or one process per GPU ([`Comm::init_rank`]).
 pub struct Comm {

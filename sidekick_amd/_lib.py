@@ -102,6 +102,9 @@ SIGNATURES = {
     "qk_u32_encode_packets_device": (C.c_int, [vp, vp, sz, sz, vp, vp, vp, vp, vp]),
     "qk_u32_encode_flows_device": (C.c_int, [vp, vp, sz, sz, vp, vp, C.c_uint32, vp, vp, sz, szp, vp, vp]),
     "qk_u32_encode_segments_device": (C.c_int, [vp, vp, u64p, sz, C.c_uint32, vp, vp]),
+    "qk_u32_to_coeffs_segments_device": (C.c_int, [vp, vp, sz, C.c_uint32, u32p, u32p, C.POINTER(C.c_int32), vp]),
+    "qk_u32_decode_segments_device": (C.c_int, [vp, vp, vp, u64p, sz, C.c_uint32, C.c_int, u64p, sz, u64p,
+                                                C.POINTER(C.c_int32), szp, vp]),
     "qk_comm_unique_id": (C.c_int, [u8p]),
     "qk_comm_create": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(vp)]),
     "qk_comm_init_rank": (C.c_int, [u8p, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),

@@ -87,6 +87,12 @@ struct qk_ctx {
     void *h_items_dev = nullptr;
     size_t h_items_bytes = 0;
 
+    // batched per-flow decode (segdecode.hip): the inverses of 1 ..
+    // QK_MAX_THRESHOLD for Newton's identities, computed once on the host and
+    // kept on the device (one table serves every threshold)
+    std::vector<uint32_t> h_seg_inv;
+    uint32_t *d_seg_inv = nullptr;
+
     // host-input pipeline: pinned staging + device chunk buffers (2 slots)
     void *h_stage[2] = {nullptr, nullptr};
     void *d_stage[2] = {nullptr, nullptr};
@@ -179,6 +185,7 @@ int warm_decode(hipStream_t s);
 int warm_packets(hipStream_t s);
 int warm_flows(hipStream_t s);
 int warm_segments(hipStream_t s);
+int warm_segdecode(hipStream_t s);
 int warm_comm(hipStream_t s);
 
 hipStream_t pick_stream(qk_ctx *ctx, void *stream);

@@ -18,6 +18,9 @@ plus the batch entry points of the MI355X engine:
                              HBM-resident path; numpy array: host path with
                              pipelined H2D).
     decode_with_log(log)     to_coeffs on the host, root test on the GPU.
+    to_coeffs_segments(..)   to_coeffs of one diff sketch per flow, one device pass.
+    decode_segments(..)      decode_with_log of many (diff, log segment) pairs,
+                             one device pass (the per-flow quACKs of SidekickMulti).
 
 Per-packet insert/remove stay on the host (one insert is far cheaper than a
 kernel launch); every batch call runs the gfx950 kernels and raises if the
@@ -30,11 +33,12 @@ import threading
 
 import numpy as np
 
-from ._lib import (P32, P64, QK_E_CAPACITY, QuackError, check, lib)
+from ._lib import (P32, P64, QK_E_CAPACITY, QK_E_MISMATCH, QuackError, check, lib)
 
 __all__ = [
     "PowerSumQuackU32", "PowerSumQuackU64", "ModularInteger", "CoefficientVector",
     "arithmetic", "Context", "get_context", "device_count", "FlowQuacks",
+    "to_coeffs_segments", "decode_segments",
 ]
 
 
@@ -477,6 +481,108 @@ def encode_segments(ids, offsets, threshold: int, ctx: Context | None = None) ->
         q._buf = C.create_string_buffer(raw[i * rec:(i + 1) * rec], rec)
         res.append(q)
     return res
+
+
+def _segment_records(diffs, threshold):
+    """(pointer, nseg, threshold, device index or None, keep-alive) of a batch
+    of diff sketches: a list of PowerSumQuackU32 of one threshold (packed into
+    host records) or a CUDA int32 tensor [nseg, 4 + t] of qk_u32 records, as
+    encode_flows(device_out=True) returns."""
+    try:
+        import torch
+    except ImportError:  # pragma: no cover
+        torch = None
+    if torch is not None and isinstance(diffs, torch.Tensor):
+        if not (diffs.is_cuda and diffs.dtype == torch.int32 and diffs.dim() == 2 and diffs.is_contiguous()
+                and diffs.shape[1] > 4):
+            raise TypeError("device diffs must be a contiguous CUDA int32 tensor [nseg, 4 + t]")
+        t = diffs.shape[1] - 4 if threshold is None else int(threshold)
+        if t != diffs.shape[1] - 4:
+            raise QuackError(QK_E_MISMATCH, "device diffs: record width is not 4 + threshold")
+        dev = diffs.device.index if diffs.device.index is not None else torch.cuda.current_device()
+        return diffs.data_ptr(), diffs.shape[0], t, dev, diffs
+    diffs = list(diffs)
+    if not diffs:
+        return None, 0, int(threshold) if threshold is not None else 1, None, None
+    t = diffs[0].threshold() if threshold is None else int(threshold)
+    for q in diffs:
+        if not isinstance(q, PowerSumQuackU32):
+            raise TypeError("diffs must be PowerSumQuackU32 sketches (the batched decode is u32 only)")
+        if q.threshold() != t:
+            raise QuackError(QK_E_MISMATCH, "diffs of different thresholds")
+    buf = C.create_string_buffer(b"".join(q._buf.raw for q in diffs))
+    return C.cast(buf, C.c_void_p), len(diffs), t, None, buf
+
+
+def to_coeffs_segments(diffs, threshold: int | None = None, ctx: Context | None = None):
+    """to_coeffs() of every diff sketch of a batch in one device pass
+    (qk_u32_to_coeffs_segments_device; media_client.rs:304 per flow of
+    sidekick_multi.rs:65-90).  Returns (coeffs, status): one CoefficientVector
+    per sketch (empty where status is QK_E_UNDECODABLE, count > threshold) and
+    the per-sketch status codes."""
+    ptr, nseg, t, dev, keep = _segment_records(diffs, threshold)
+    ctx = ctx or get_context(dev or 0)
+    stream = None
+    if dev is not None:
+        import torch
+        stream = torch.cuda.current_stream(dev).cuda_stream
+    coeffs = np.zeros((max(nseg, 1), t), dtype=np.uint32)
+    deg = np.zeros(max(nseg, 1), dtype=np.uint32)
+    status = np.zeros(max(nseg, 1), dtype=np.int32)
+    check(lib().qk_u32_to_coeffs_segments_device(ctx.handle, ptr, nseg, t, coeffs.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                  deg.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                  status.ctypes.data_as(C.POINTER(C.c_int32)), stream),
+          "to_coeffs_segments")
+    del keep
+    return ([CoefficientVector(coeffs[g, :deg[g]].tolist(), 32) for g in range(nseg)],
+            [int(s) for s in status[:nseg]])
+
+
+def decode_segments(diffs, log, offsets, stop_at_last: bool = False, ctx: Context | None = None):
+    """decode_with_log for a batch of flows in one device pass
+    (qk_u32_decode_segments_device): `diffs` one diff sketch per flow (a list
+    of PowerSumQuackU32 of one threshold, or the CUDA int32 record tensor of
+    encode_flows(device_out=True)), `log` a CUDA u32/int32 tensor grouped by
+    flow, `offsets` nseg + 1 ints (CSR).  Returns (positions, status):
+    positions[g] are the positions, local to segment g, of its missing
+    entries, equal to diffs[g].decode_host(log[offsets[g]:offsets[g+1]],
+    stop_at_last); status[g] is QK_OK or QK_E_UNDECODABLE (no positions)."""
+    ptr, nseg, t, _, keep = _segment_records(diffs, None)
+    d_log = _device_array(log, 32)
+    if d_log is None:
+        import torch  # a host log: one H2D copy (raises with no device: there is no CPU path)
+        ctx = ctx or get_context(0)
+        log = torch.from_numpy(_host_array(log, 32).view(np.int32)).to(f"cuda:{ctx.device}")
+        d_log = _device_array(log, 32)
+    lptr, n, dev, stream = d_log
+    ctx = ctx or get_context(dev)
+    offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64))
+    if len(offs) != nseg + 1:
+        raise ValueError("offsets must hold one entry more than diffs")
+    if nseg and int(offs[-1]) > n:
+        raise ValueError("offsets run past the end of log")
+    hoffs = np.zeros(nseg + 1, dtype=np.uint64)
+    status = np.zeros(max(nseg, 1), dtype=np.int32)
+    cap = max(1024, 4 * nseg)
+    while True:
+        hits = np.empty(max(cap, 1), dtype=np.uint64)
+        nh = C.c_size_t()
+        rc = lib().qk_u32_decode_segments_device(ctx.handle, ptr, lptr, offs.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                 nseg, t, int(bool(stop_at_last)),
+                                                 hits.ctypes.data_as(C.POINTER(C.c_uint64)), cap,
+                                                 hoffs.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                 status.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(nh), stream)
+        if rc == QK_E_CAPACITY:
+            cap = nh.value
+            continue
+        check(rc, "decode_segments")
+        break
+    del keep
+    out = []
+    for g in range(nseg):
+        a, b = int(hoffs[g]), int(hoffs[g + 1])
+        out.append((hits[a:b] - offs[g]).tolist())
+    return out, [int(s) for s in status[:nseg]]
 
 
 def encode_flows(bufs, threshold: int, stride: int = 67, meta=None, my_addr=None, ctx: Context | None = None,

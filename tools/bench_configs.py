@@ -9,6 +9,9 @@
   sweep    encode rate vs threshold t (u32)
   packets  sniff-loop batch: 67-byte records in HBM -> one quACK
   flows    per-flow batch: records of 16 / 1e4 / 1e6 flows -> one quACK each
+  segdecode  batched per-flow decode: 1e8 log entries of 1e6 flows, t=32, 0-8
+           entries missing per flow, against the one-core host loop and the
+           per-flow device call over a prefix of the flows
   micro    reference-shape rows (1000 ids x 100 trials) and configs[0]
 
 Each prints one JSON line per measurement.  Kernel times come from HIP events
@@ -260,6 +263,144 @@ def run_flows(args, ctx):
         del f
 
 
+def run_segdecode(args, ctx):
+    """Batched per-flow decode (qk_u32_decode_segments_device) at the shape of
+    the per-flow batch: --npkts log entries in --nflows flows (Poisson
+    lengths), t = 32, each flow's diff built from 0-8 dropped entries of its
+    own segment, stop_at_last on.  Beside it, on the same data, the two routes
+    there were before: qk_u32_decode_host in a one-core loop over the first
+    1e4 flows and qk_u32_decode_device over the first 1e3, scaled to all."""
+    import ctypes as C
+    from sidekick_amd._lib import lib
+    L = lib()
+    t, nflows = 32, int(args.nflows)
+    rng = np.random.default_rng(0x5E6DEC)
+    lens = rng.poisson(args.npkts / nflows, size=nflows).astype(np.int64)
+    offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64)
+    n = int(offs[-1])
+    log = torch.empty(n, dtype=torch.int32, device=DEV)
+    fill_splitmix(ctx, log, 0x5EED0007)
+    # 0-8 drops per flow at random places of its segment (drawn with
+    # replacement: a repeated place is one drop)
+    k = rng.integers(0, 9, size=nflows)
+    place = np.floor(rng.random((nflows, 8)) * lens[:, None]).astype(np.int64) + offs[:-1, None].astype(np.int64)
+    use = (np.arange(8)[None, :] < k[:, None]) & (lens[:, None] > 0)
+    drop_pos = np.unique(place[use])
+    keep = torch.ones(n, dtype=torch.bool, device=DEV)
+    keep[torch.from_numpy(drop_pos).to(DEV)] = False
+    kept = log[keep].contiguous()
+    del keep
+    ndrop = np.bincount(np.searchsorted(offs, drop_pos, side="right") - 1, minlength=nflows)
+    kept_offs = (offs - np.concatenate([[0], np.cumsum(ndrop)]).astype(np.uint64)).astype(np.uint64)
+    rsz = L.qk_u32_size(t)
+    u64p = C.POINTER(C.c_uint64)
+
+    def encode(ids, o):
+        out = np.zeros((nflows, rsz // 4), dtype=np.uint32)
+        rc = L.qk_u32_encode_segments_device(ctx.handle, ids.data_ptr(), o.ctypes.data_as(u64p), nflows, t,
+                                             out.ctypes.data, 0)
+        if rc:
+            raise RuntimeError(f"encode_segments rc={rc}")
+        return out
+    diff, recv = encode(log, offs), encode(kept, kept_offs)
+    del kept
+    dbase, rbase = diff.ctypes.data, recv.ctypes.data
+    for g in range(nflows):                      # diff_quack.sub_assign(quack), per flow
+        L.qk_u32_sub_assign(dbase + g * rsz, rbase + g * rsz)
+    del recv
+    assert np.array_equal(diff[:, 1], ndrop.astype(np.uint32))
+    cap = int(ndrop.sum()) + 1024
+    hits = np.zeros(cap, dtype=np.uint64)
+    hoffs = np.zeros(nflows + 1, dtype=np.uint64)
+    status = np.zeros(nflows, dtype=np.int32)
+    nh = C.c_size_t()
+
+    def batched(records=None):
+        rc = L.qk_u32_decode_segments_device(ctx.handle, records or diff.ctypes.data, log.data_ptr(),
+                                             offs.ctypes.data_as(u64p),
+                                             nflows, t, 1, hits.ctypes.data_as(u64p), cap, hoffs.ctypes.data_as(u64p),
+                                             status.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(nh), 0)
+        if rc:
+            raise RuntimeError(f"decode_segments rc={rc}")
+    for _ in range(3):
+        batched()
+    walls = []
+    for _ in range(max(20, args.steps)):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        batched()
+        walls.append(time.perf_counter() - t0)
+    # the same call on records that are already in HBM (encode_flows(device_out=True)): no 144 MB H2D copy
+    d_diff = torch.from_numpy(diff.view(np.int32)).to(DEV)
+    walls_dev = []
+    for it in range(max(20, args.steps) + 3):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        batched(d_diff.data_ptr())
+        if it >= 3:
+            walls_dev.append(time.perf_counter() - t0)
+    del d_diff
+    # kernel times: the Newton kernel alone (to_coeffs), then Newton + root test (decode)
+    coeffs = np.zeros((nflows, t), dtype=np.uint32)
+    deg = np.zeros(nflows, dtype=np.uint32)
+    newton, both = [], []
+    ctx.kernel_stats()
+    ctx.set_profiling(True)
+    for _ in range(5):
+        rc = L.qk_u32_to_coeffs_segments_device(ctx.handle, diff.ctypes.data, nflows, t,
+                                                coeffs.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                deg.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                status.ctypes.data_as(C.POINTER(C.c_int32)), 0)
+        if rc:
+            raise RuntimeError(f"to_coeffs_segments rc={rc}")
+        newton.append(ctx.kernel_stats()[0])
+        batched()
+        both.append(ctx.kernel_stats()[0])
+    ctx.set_profiling(False)
+    newton_ms = float(np.median(newton))
+    rt_ms = float(np.median(both)) - newton_ms
+    # the routes of the parent code, on a prefix of the same flows
+    m_host, m_dev = min(10_000, nflows), min(1_000, nflows)
+    h_log = log[:int(offs[m_host])].cpu().numpy().view(np.uint32)
+    hh = np.zeros(4096, dtype=np.uint64)
+    hp, lp, dp = hh.ctypes.data_as(u64p), h_log.ctypes.data, diff.ctypes.data
+    u32p = C.POINTER(C.c_uint32)
+    args_host = [(C.c_void_p(dp + g * rsz), C.cast(lp + 4 * int(offs[g]), u32p), int(offs[g + 1] - offs[g]))
+                 for g in range(m_host)]
+    host_hits = []
+    t0 = time.perf_counter()
+    for q, lg, ln in args_host:
+        L.qk_u32_decode_host(q, lg, ln, 1, hp, 4096, C.byref(nh))
+        host_hits.append(hh[:nh.value].tolist())
+    host_s = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    for q, lg, ln in args_host:                   # the same loop around an empty log: what the loop itself costs
+        L.qk_u32_decode_host(q, lg, 0, 1, hp, 4096, C.byref(nh))
+        hh[:nh.value].tolist()
+    loop_s = time.perf_counter() - t0
+    parity = all(host_hits[g] == (hits[int(hoffs[g]):int(hoffs[g + 1])] - offs[g]).tolist() for g in range(m_host))
+    for rep in range(2):                          # the second pass is the warm one
+        t0 = time.perf_counter()
+        for g in range(m_dev):
+            rc = L.qk_u32_decode_device(ctx.handle, dp + g * rsz, log.data_ptr() + 4 * int(offs[g]),
+                                        int(offs[g + 1] - offs[g]), 1, hp, 4096, C.byref(nh), 0)
+            if rc:
+                raise RuntimeError(f"decode_device rc={rc}")
+        dev_s = time.perf_counter() - t0
+    wall = float(np.median(walls))
+    host_scaled = (host_s - loop_s) * nflows / m_host
+    emit({"config": f"batched per-flow decode: {n} log entries of {nflows} flows, t={t}, 0-8 missing per flow, "
+                    "stop_at_last", "n": n, "flows": nflows, "hits": int(hoffs[-1]), "calls": len(walls),
+          "wall_ms_median": wall * 1e3, "wall_ms_min": min(walls) * 1e3, "wall_ms_max": max(walls) * 1e3,
+          "wall_ms_median_device_records": float(np.median(walls_dev)) * 1e3,
+          "newton_kernel_ms": newton_ms, "root_test_kernel_ms": rt_ms,
+          "root_test_log_GBps": 4 * n / (rt_ms * 1e-3) / 1e9, "frac_hbm_8TBs": 4 * n / (rt_ms * 1e-3) / 8e12,
+          "host_loop_flows": m_host, "host_loop_s": host_s, "host_loop_overhead_s": loop_s,
+          "host_loop_scaled_s": host_scaled, "device_loop_flows": m_dev, "device_loop_us_per_call": dev_s / m_dev * 1e6,
+          "device_loop_scaled_s": dev_s * nflows / m_dev, "parity": bool(parity),
+          "speedup_vs_host_loop": host_scaled / wall, "speedup_vs_device_loop": dev_s * nflows / m_dev / wall})
+
+
 # published quack-crate encode ns/id, 1000 ids per trial, 1 Xeon core
 # (BASELINE.md table: zip:nsdi24/quack/threshold_vs_encode_time/{32,64}.txt)
 PUBLISHED_NS = {(32, 10): 34, (32, 20): 75, (32, 30): 117, (32, 40): 161, (32, 80): 327,
@@ -343,8 +484,10 @@ def run_sweep64(args, ctx):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pkt-t", default="32", help="packets: thresholds (comma list)")
-    ap.add_argument("what", nargs="+", choices=["u64", "decode", "decode64", "host", "sweep", "sweep64", "packets", "flows", "micro"])
+    ap.add_argument("what", nargs="+", choices=["u64", "decode", "decode64", "host", "sweep", "sweep64", "packets", "flows", "segdecode",
+                                                 "micro"])
     ap.add_argument("--npkts", type=float, default=1e8)
+    ap.add_argument("--nflows", type=float, default=1e6, help="segdecode: flows")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--n64", type=float, default=1e9)
     ap.add_argument("--ndec", type=float, default=1e8)
@@ -368,7 +511,7 @@ def main():
             ctx.set_knob(k, int(v))
     for w in args.what:
         {"u64": run_u64, "decode": run_decode, "decode64": run_decode64, "host": run_host, "sweep": run_sweep, "sweep64": run_sweep64,
-         "packets": run_packets, "flows": run_flows, "micro": run_micro}[w](args, ctx)
+         "packets": run_packets, "flows": run_flows, "segdecode": run_segdecode, "micro": run_micro}[w](args, ctx)
         torch.cuda.empty_cache()
 
 
