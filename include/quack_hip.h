@@ -366,6 +366,62 @@ int qk_u32_decode_segments_device(qk_ctx *ctx, const uint8_t *diffs, const uint3
                                   size_t *n_hits, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Device-resident flow table: SidekickMulti's `senders: HashMap<AddrKey,
+ * PowerSumQuackU32>` (sidekick_multi.rs:36,65-90) kept in HBM as a "flow
+ * array": n qk_flow_key plus n qk_u32 records of qk_u32_size(threshold) bytes,
+ * keys strictly ascending in memcmp order of their 12 bytes — exactly what
+ * qk_u32_encode_flows_device writes.  The three calls are stateless: the
+ * caller owns every table buffer, the context supplies scratch only.  Every
+ * flow array is device memory of ctx's GPU, 4-byte aligned, n < 2^31.  All
+ * three are synchronous on `stream`.  A host pointer where a device pointer is
+ * required, a misaligned array, or an output range that overlaps an input
+ * range -> QK_E_INVAL.  Input keys that are not strictly ascending (an
+ * adjacent pair out of order or equal, in a or in b; found on the device
+ * during the join) -> QK_E_INVAL; a record whose threshold field differs from
+ * `threshold` -> QK_E_MISMATCH; after either the outputs are unspecified.
+ * Sizes of 0 are valid (merge copies, diff copies a, lookup finds nothing).
+ * ---------------------------------------------------------------------- */
+#define QK_FLOW_JOIN_TILE 2048u   /* keys of a and b together per work item of the join */
+
+/* table ∪ batch: the per-flow `senders.entry(key).or_insert(new).insert(id)`
+ * of sidekick_multi.rs:65-90 for a whole encoded batch.
+ * Key in both: qk_u32_merge(a_rec, b_rec), b the later stream.
+ * Key in one only: that record, copied.
+ * Output ascending.
+ * due_out (device, cap bytes, may be NULL): due_out[r] = 1 iff output r has a b source and
+ *   (before + b.count) / frequency_pkts > before / frequency_pkts, evaluated in 64 bits,
+ *   where before = the a source's count, or 0 without one.
+ *   This flags the flows for which start_sidekick_multi_frequency_pkts
+ *   (sidekick_multi.rs:274) would have emitted during the batch; the quACK a
+ *   caller then sends is the end-of-batch one, not a mid-batch snapshot.
+ *   0 otherwise, and all 0 when frequency_pkts == 0.
+ * *n_out = flows in the union.
+ * cap < *n_out -> QK_E_CAPACITY with *n_out set and no output array written. */
+int qk_u32_flows_merge_device(qk_ctx *ctx, const qk_flow_key *d_keys_a, const uint8_t *d_sk_a, size_t na,
+                              const qk_flow_key *d_keys_b, const uint8_t *d_sk_b, size_t nb, uint32_t threshold,
+                              uint32_t frequency_pkts, qk_flow_key *d_keys_out, uint8_t *d_sk_out,
+                              uint8_t *d_due_out, size_t cap, size_t *n_out, void *stream);
+
+/* media_client.rs:295-296 for every flow of a (mine) against b (the peer's quACKs).
+ * d_diffs_out[i] = a[i], and where a's key i is in b, qk_u32_sub_assign by that b record
+ *   (sums subtract mod p, count wraps, last_value stays a's).
+ * na records in a's key order: what qk_u32_decode_segments_device takes.
+ * b keys absent from a are ignored.
+ * *n_matched = keys present in both. */
+int qk_u32_flows_diff_device(qk_ctx *ctx, const qk_flow_key *d_keys_a, const uint8_t *d_sk_a, size_t na,
+                             const qk_flow_key *d_keys_b, const uint8_t *d_sk_b, size_t nb, uint32_t threshold,
+                             uint8_t *d_diffs_out, size_t *n_matched, void *stream);
+
+/* SidekickMulti::quack(&addr_key) (sidekick_multi.rs:92-94) for nk keys.
+ * keys, sketches and found are HOST memory.
+ * keys may come in any order, repeats allowed.
+ * found[i] = 1 and sketches record i = the flow's record when the key is in the table.
+ * Otherwise found[i] = 0 and record i = qk_u32_init(threshold). */
+int qk_u32_flows_lookup_device(qk_ctx *ctx, const qk_flow_key *d_keys, const uint8_t *d_sk, size_t n,
+                               uint32_t threshold, const qk_flow_key *keys, size_t nk, uint8_t *sketches,
+                               uint8_t *found, void *stream);
+
+/* ------------------------------------------------------------------------
  * Multi-GPU: the id stream cut into contiguous shards, one
  * per GPU in global rank order, merged with ONE RCCL reduce over xGMI.
  * The reference callers are single processes (sidekick.rs:58-127,

@@ -20,6 +20,7 @@ pub const QK_MAX_THRESHOLD: u32 = 1024;
 pub const QK_ID_OFFSET: usize = 63;
 pub const QK_BUFFER_SIZE: usize = 67;
 pub const QK_COMM_ID_BYTES: usize = 128;
+pub const QK_FLOW_JOIN_TILE: u32 = 2048;
 
 pub const QK_OK: c_int = 0;
 pub const QK_E_INVAL: c_int = -1;
@@ -218,6 +219,19 @@ extern "C" {
                                          offsets: *const u64, nseg: usize, threshold: u32, stop_at_last: c_int,
                                          hits: *mut u64, cap: usize, hit_offsets: *mut u64, status: *mut int32_t,
                                          n_hits: *mut usize, stream: *mut c_void) -> c_int;
+
+    // device-resident flow table
+    pub fn qk_u32_flows_merge_device(ctx: *mut qk_ctx, d_keys_a: *const qk_flow_key, d_sk_a: *const u8, na: usize,
+                                     d_keys_b: *const qk_flow_key, d_sk_b: *const u8, nb: usize, threshold: u32,
+                                     frequency_pkts: u32, d_keys_out: *mut qk_flow_key, d_sk_out: *mut u8,
+                                     d_due_out: *mut u8, cap: usize, n_out: *mut usize,
+                                     stream: *mut c_void) -> c_int;
+    pub fn qk_u32_flows_diff_device(ctx: *mut qk_ctx, d_keys_a: *const qk_flow_key, d_sk_a: *const u8, na: usize,
+                                    d_keys_b: *const qk_flow_key, d_sk_b: *const u8, nb: usize, threshold: u32,
+                                    d_diffs_out: *mut u8, n_matched: *mut usize, stream: *mut c_void) -> c_int;
+    pub fn qk_u32_flows_lookup_device(ctx: *mut qk_ctx, d_keys: *const qk_flow_key, d_sk: *const u8, n: usize,
+                                      threshold: u32, keys: *const qk_flow_key, nk: usize, sketches: *mut u8,
+                                      found: *mut u8, stream: *mut c_void) -> c_int;
 
     // multi-GPU over RCCL
     pub fn qk_comm_unique_id(id: *mut u8) -> c_int;

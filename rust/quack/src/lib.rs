@@ -587,6 +587,68 @@ pub unsafe fn decode_segments_device(ctx: &Context, diffs: &[PowerSumQuackU32], 
     }
 }
 
+/// A flow array in device memory: `n` keys, strictly ascending in byte order,
+/// and `n` `qk_u32` records of one threshold — `SidekickMulti`'s `senders`
+/// (`sidekick_multi.rs:36`) as [`encode_flows_device`]'s device output lays it
+/// out.  The caller owns both buffers.
+#[derive(Clone, Copy)]
+pub struct DeviceFlows {
+    pub keys: *const ffi::qk_flow_key,
+    pub sketches: *const u8,
+    pub n: usize,
+}
+
+/// table ∪ batch on the device (`sidekick_multi.rs:65-90` for a whole encoded
+/// batch, `b` the later stream): returns the flows of the union, written to
+/// `keys_out` / `sketches_out` (room for `cap` flows; `QK_E_CAPACITY` when the
+/// union is larger).  `due_out` (device, `cap` bytes, or null) flags the flows
+/// whose count crossed a multiple of `frequency_pkts` during the batch
+/// (`sidekick_multi.rs:274`); the quACK to send is the end-of-batch one.
+///
+/// # Safety
+/// Every pointer must be device memory of `ctx`'s GPU of the stated size, the
+/// outputs apart from the inputs.
+pub unsafe fn flows_merge_device(ctx: &Context, a: DeviceFlows, b: DeviceFlows, threshold: u32, frequency_pkts: u32,
+                                 keys_out: *mut ffi::qk_flow_key, sketches_out: *mut u8, due_out: *mut u8,
+                                 cap: usize, stream: *mut c_void) -> Result<usize> {
+    let mut n_out = 0usize;
+    check(ffi::qk_u32_flows_merge_device(ctx.raw, a.keys, a.sketches, a.n, b.keys, b.sketches, b.n, threshold,
+                                         frequency_pkts, keys_out, sketches_out, due_out, cap, &mut n_out, stream))?;
+    Ok(n_out)
+}
+
+/// `diff_quack = my_quack.clone(); diff_quack.sub_assign(quack)`
+/// (`media_client.rs:295-296`) for every flow of `a` (mine) against `b` (the
+/// peer's): `a.n` records into `diffs_out` in `a`'s key order, ready for
+/// [`decode_segments_device`]'s device form.  Returns the keys found in both.
+///
+/// # Safety
+/// Every pointer must be device memory of `ctx`'s GPU of the stated size.
+pub unsafe fn flows_diff_device(ctx: &Context, a: DeviceFlows, b: DeviceFlows, threshold: u32, diffs_out: *mut u8,
+                                stream: *mut c_void) -> Result<usize> {
+    let mut matched = 0usize;
+    check(ffi::qk_u32_flows_diff_device(ctx.raw, a.keys, a.sketches, a.n, b.keys, b.sketches, b.n, threshold,
+                                        diffs_out, &mut matched, stream))?;
+    Ok(matched)
+}
+
+/// `SidekickMulti::quack(&addr_key)` (`sidekick_multi.rs:92-94`) for a list of
+/// keys against a device flow array: `None` where the table has no such flow.
+///
+/// # Safety
+/// `table` must describe device memory of `ctx`'s GPU.
+pub unsafe fn flows_lookup_device(ctx: &Context, table: DeviceFlows, threshold: u32, keys: &[ffi::qk_flow_key],
+                                  stream: *mut c_void) -> Result<Vec<Option<PowerSumQuackU32>>> {
+    let words = ffi::qk_u32_size(threshold) / 4;
+    let mut rec = vec![0u32; keys.len().max(1) * words];
+    let mut found = vec![0u8; keys.len().max(1)];
+    check(ffi::qk_u32_flows_lookup_device(ctx.raw, table.keys, table.sketches, table.n, threshold, keys.as_ptr(),
+                                          keys.len(), rec.as_mut_ptr() as *mut u8, found.as_mut_ptr(), stream))?;
+    Ok((0..keys.len())
+        .map(|i| (found[i] != 0).then(|| PowerSumQuackU32 { words: rec[i * words..(i + 1) * words].to_vec() }))
+        .collect())
+}
+
 /// Multi-GPU communicator over RCCL (xGMI): one process driving several
 /// GPUs ([`Comm::new`]) or one process per GPU ([`Comm::init_rank`]).
 pub struct Comm {

@@ -1,8 +1,9 @@
 """sidekick_amd — MI355X-native quACK power-sum engine (gfx950 HIP kernels
 behind the C ABI in include/quack_hip.h).  See DESIGN.md."""
 from .quack import (  # noqa: F401
-    CoefficientVector, Context, FlowQuacks, ModularInteger, PowerSumQuackU32, PowerSumQuackU64,
-    arithmetic, decode_segments, device_count, get_context, roots, to_coeffs_segments,
+    CoefficientVector, Context, DeviceFlowQuacks, FlowQuacks, ModularInteger, PowerSumQuackU32, PowerSumQuackU64,
+    arithmetic, decode_segments, device_count, flows_diff, flows_lookup, flows_merge, get_context, roots,
+    to_coeffs_segments,
 )
 from ._lib import P32, P64, QuackError, UndecodableError  # noqa: F401
 

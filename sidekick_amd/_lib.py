@@ -30,6 +30,7 @@ QK_E_PEER = -11
 P32 = 4294967291
 P64 = 18446744073709551557
 MAX_THRESHOLD = 1024
+FLOW_JOIN_TILE = 2048   # QK_FLOW_JOIN_TILE: keys of a and b together per work item of the flow-table join
 
 u8p = C.POINTER(C.c_uint8)
 u32p = C.POINTER(C.c_uint32)
@@ -105,6 +106,10 @@ SIGNATURES = {
     "qk_u32_to_coeffs_segments_device": (C.c_int, [vp, vp, sz, C.c_uint32, u32p, u32p, C.POINTER(C.c_int32), vp]),
     "qk_u32_decode_segments_device": (C.c_int, [vp, vp, vp, u64p, sz, C.c_uint32, C.c_int, u64p, sz, u64p,
                                                 C.POINTER(C.c_int32), szp, vp]),
+    "qk_u32_flows_merge_device": (C.c_int, [vp, vp, vp, sz, vp, vp, sz, C.c_uint32, C.c_uint32, vp, vp, vp, sz, szp,
+                                            vp]),
+    "qk_u32_flows_diff_device": (C.c_int, [vp, vp, vp, sz, vp, vp, sz, C.c_uint32, vp, szp, vp]),
+    "qk_u32_flows_lookup_device": (C.c_int, [vp, vp, vp, sz, C.c_uint32, vp, sz, vp, vp, vp]),
     "qk_comm_unique_id": (C.c_int, [u8p]),
     "qk_comm_create": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(vp)]),
     "qk_comm_init_rank": (C.c_int, [u8p, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),

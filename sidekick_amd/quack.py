@@ -21,6 +21,9 @@ plus the batch entry points of the MI355X engine:
     to_coeffs_segments(..)   to_coeffs of one diff sketch per flow, one device pass.
     decode_segments(..)      decode_with_log of many (diff, log segment) pairs,
                              one device pass (the per-flow quACKs of SidekickMulti).
+    flows_merge / flows_diff / flows_lookup, DeviceFlowQuacks
+                             SidekickMulti's flow table as key-sorted arrays in
+                             HBM: merge a batch, diff against a peer, look up.
 
 Per-packet insert/remove stay on the host (one insert is far cheaper than a
 kernel launch); every batch call runs the gfx950 kernels and raises if the
@@ -39,6 +42,7 @@ __all__ = [
     "PowerSumQuackU32", "PowerSumQuackU64", "ModularInteger", "CoefficientVector",
     "arithmetic", "Context", "get_context", "device_count", "FlowQuacks",
     "to_coeffs_segments", "decode_segments",
+    "flows_merge", "flows_diff", "flows_lookup", "DeviceFlowQuacks",
 ]
 
 
@@ -586,13 +590,15 @@ def decode_segments(diffs, log, offsets, stop_at_last: bool = False, ctx: Contex
 
 
 def encode_flows(bufs, threshold: int, stride: int = 67, meta=None, my_addr=None, ctx: Context | None = None,
-                 device_out: bool = False):
+                 device_out: bool = False, cap: int = 1024):
     """One SidekickMulti batch (sidekick_multi.rs:65-90,101-143) without the
     table merge: returns (keys, sketches, stats) for the batch's flows in
     ascending AddrKey order.  device_out=False: keys is a list of 12-byte
     AddrKeys and sketches a list of PowerSumQuackU32.  device_out=True: both
     stay in HBM as CUDA tensors (uint8 [nf, 12] and int32 [nf, 4 + t], the
-    qk_u32 records), written in place by the finalize kernel."""
+    qk_u32 records), written in place by the finalize kernel.  `cap` is the
+    flow count the outputs are first sized for (a batch of more flows runs a
+    second time with the size the first run reports)."""
     import torch
     if not (isinstance(bufs, torch.Tensor) and bufs.is_cuda and bufs.dtype == torch.uint8 and bufs.is_contiguous()):
         raise TypeError("bufs must be a contiguous CUDA uint8 tensor")
@@ -607,7 +613,7 @@ def encode_flows(bufs, threshold: int, stride: int = 67, meta=None, my_addr=None
     addr = (C.c_uint8 * 6)(*my_addr) if my_addr is not None else None
     rec = lib().qk_u32_size(threshold)
     stream = torch.cuda.current_stream(dev).cuda_stream
-    cap = 1024
+    cap = max(int(cap), 1)
     while True:
         nf, st = C.c_size_t(), PktStats()
         if device_out:
@@ -686,6 +692,232 @@ class FlowQuacks:
             else:
                 old.merge(q)
         return stats
+
+
+# --------------------------------------------------------------------------
+# The flow table in HBM: key-sorted flow arrays and the three device calls
+# --------------------------------------------------------------------------
+def _quack_from_bytes(raw: bytes, threshold: int) -> "PowerSumQuackU32":
+    q = PowerSumQuackU32.__new__(PowerSumQuackU32)
+    q._t = threshold
+    q._buf = C.create_string_buffer(raw, len(raw))
+    return q
+
+
+def _flow_ctx(ctx, *tensors) -> Context:
+    """The context of a flow-table call, resolved before anything else: with no
+    device this raises QK_E_NO_DEVICE whatever the arguments are."""
+    if ctx is not None:
+        return ctx
+    for a in tensors:
+        if getattr(a, "is_cuda", False):
+            import torch
+            return get_context(a.device.index if a.device.index is not None else torch.cuda.current_device())
+    return get_context(0)
+
+
+def _flow_array(keys, sk, what: str):
+    """(n, threshold) of a flow array: `keys` a CUDA uint8 tensor [n, 12], `sk` a
+    CUDA int32 tensor [n, 4 + t] of qk_u32 records, both contiguous, as
+    encode_flows(device_out=True) returns them."""
+    import torch
+    ok = (isinstance(keys, torch.Tensor) and isinstance(sk, torch.Tensor) and keys.is_cuda and sk.is_cuda
+          and keys.dtype == torch.uint8 and sk.dtype == torch.int32 and keys.dim() == 2 and sk.dim() == 2
+          and keys.shape[1] == 12 and sk.shape[1] > 4 and keys.shape[0] == sk.shape[0]
+          and keys.is_contiguous() and sk.is_contiguous())
+    if not ok:
+        raise TypeError(f"{what}: a flow array is a contiguous CUDA uint8 [n, 12] key tensor and a contiguous CUDA "
+                        "int32 [n, 4 + t] record tensor of the same n")
+    return keys.shape[0], sk.shape[1] - 4
+
+
+def _flow_pair(keys_a, sk_a, keys_b, sk_b):
+    na, t = _flow_array(keys_a, sk_a, "a")
+    nb, tb = _flow_array(keys_b, sk_b, "b")
+    if t != tb:
+        raise QuackError(QK_E_MISMATCH, "flow arrays of different thresholds")
+    if keys_b.device != keys_a.device:
+        raise ValueError("flow arrays on different devices")
+    return na, nb, t
+
+
+def _flow_stream(t):
+    import torch
+    return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def flows_merge(keys_a, sk_a, keys_b, sk_b, frequency_pkts: int = 0, ctx: Context | None = None):
+    """table ∪ batch on the device (qk_u32_flows_merge_device; the per-flow
+    insert of sidekick_multi.rs:65-90 for a whole encoded batch): a and b are
+    flow arrays as encode_flows(device_out=True) returns them, b the later
+    stream.  Returns (keys, sketches, due): the union in ascending key order
+    and a uint8 tensor flagging the flows whose count crossed a multiple of
+    frequency_pkts during b (all 0 when it is 0).  The outputs are views of
+    na + nb freshly allocated rows, so the call never retries."""
+    import torch
+    ctx = _flow_ctx(ctx, keys_a, keys_b)
+    na, nb, t = _flow_pair(keys_a, sk_a, keys_b, sk_b)
+    cap = na + nb
+    keys = torch.empty((cap, 12), dtype=torch.uint8, device=keys_a.device)
+    sk = torch.empty((cap, 4 + t), dtype=torch.int32, device=keys_a.device)
+    due = torch.empty((cap,), dtype=torch.uint8, device=keys_a.device)
+    n = C.c_size_t()
+    check(lib().qk_u32_flows_merge_device(ctx.handle, keys_a.data_ptr(), sk_a.data_ptr(), na, keys_b.data_ptr(),
+                                          sk_b.data_ptr(), nb, t, int(frequency_pkts), keys.data_ptr(),
+                                          sk.data_ptr(), due.data_ptr(), cap, C.byref(n), _flow_stream(keys_a)),
+          "flows_merge")
+    return keys[:n.value], sk[:n.value], due[:n.value]
+
+
+def flows_diff(keys_a, sk_a, keys_b, sk_b, ctx: Context | None = None):
+    """media_client.rs:295-296 for every flow of a (mine) against b (the
+    peer's quACKs) on the device (qk_u32_flows_diff_device).  Returns (diffs,
+    n_matched): diffs is the CUDA int32 record tensor [na, 4 + t] in a's key
+    order — a[i] minus its b record where the key is in b, a[i] itself
+    otherwise — which decode_segments accepts unchanged."""
+    import torch
+    ctx = _flow_ctx(ctx, keys_a, keys_b)
+    na, nb, t = _flow_pair(keys_a, sk_a, keys_b, sk_b)
+    out = torch.empty((na, 4 + t), dtype=torch.int32, device=keys_a.device)
+    m = C.c_size_t()
+    check(lib().qk_u32_flows_diff_device(ctx.handle, keys_a.data_ptr(), sk_a.data_ptr(), na, keys_b.data_ptr(),
+                                         sk_b.data_ptr(), nb, t, out.data_ptr(), C.byref(m), _flow_stream(keys_a)),
+          "flows_diff")
+    return out, m.value
+
+
+def flows_lookup(keys, sk, query, ctx: Context | None = None) -> list:
+    """SidekickMulti::quack(&addr_key) (sidekick_multi.rs:92-94) for a list of
+    12-byte AddrKeys against a flow array (qk_u32_flows_lookup_device): one
+    PowerSumQuackU32 per queried key, None where the table has no such flow.
+    Any order, repeats allowed."""
+    ctx = _flow_ctx(ctx, keys)
+    n, t = _flow_array(keys, sk, "table")
+    query = [bytes(k) for k in query]
+    if any(len(k) != 12 for k in query):
+        raise ValueError("an AddrKey is 12 bytes")
+    nk = len(query)
+    if nk == 0:
+        return []
+    rec = lib().qk_u32_size(t)
+    hk = C.create_string_buffer(b"".join(query), nk * 12)
+    out = C.create_string_buffer(nk * rec)
+    found = C.create_string_buffer(nk)
+    check(lib().qk_u32_flows_lookup_device(ctx.handle, keys.data_ptr(), sk.data_ptr(), n, t, hk, nk, out, found,
+                                           _flow_stream(keys)), "flows_lookup")
+    raw, f = out.raw, found.raw
+    return [_quack_from_bytes(raw[i * rec:(i + 1) * rec], t) if f[i] else None for i in range(nk)]
+
+
+class DeviceFlowQuacks:
+    """SidekickMulti's flow table (sidekick_multi.rs:36,65-90) resident in HBM:
+    FlowQuacks' surface over a key-sorted flow array.  A batch goes
+    encode_flows -> merge without a record crossing PCIe; `diff` feeds
+    decode_segments the same way.  Two buffers, grown geometrically, take
+    turns as the merge output; `.keys` / `.sketches` are views of the current
+    one, valid until the next update."""
+
+    def __init__(self, threshold: int, device: int = 0):
+        self.threshold = int(threshold)
+        self.device = int(device)
+        self._bufs = [None, None]   # (keys, sketches, due) tensors
+        self._cur = 0
+        self._n = 0
+        self._batch_cap = 1024
+
+    def __len__(self) -> int:
+        return self._n
+
+    def _empty(self):
+        import torch
+        dev = f"cuda:{self.device}"
+        return (torch.empty((0, 12), dtype=torch.uint8, device=dev),
+                torch.empty((0, 4 + self.threshold), dtype=torch.int32, device=dev))
+
+    @property
+    def keys(self):
+        return self._bufs[self._cur][0][:self._n] if self._n else self._empty()[0]
+
+    @property
+    def sketches(self):
+        return self._bufs[self._cur][1][:self._n] if self._n else self._empty()[1]
+
+    def clear(self) -> None:
+        """`senders = HashMap::new()` (sidekick_multi.rs:205,265)."""
+        self._n = 0
+
+    def merge(self, keys, sketches, frequency_pkts: int = 0, ctx: Context | None = None):
+        """Merge a flow array (the later stream) into the table; returns the
+        `due` flags of the new table (a view, valid until the next update)."""
+        import torch
+        ctx = ctx or get_context(self.device)
+        nb, t = _flow_array(keys, sketches, "batch")
+        if t != self.threshold:
+            raise QuackError(QK_E_MISMATCH, "batch threshold differs from the table's")
+        ka, sa = self.keys, self.sketches
+        need, o = self._n + nb, 1 - self._cur
+        if self._bufs[o] is None or self._bufs[o][0].shape[0] < need:
+            rows = max(need, 1024, 2 * (self._bufs[o][0].shape[0] if self._bufs[o] is not None else 0))
+            dev = f"cuda:{self.device}"
+            self._bufs[o] = (torch.empty((rows, 12), dtype=torch.uint8, device=dev),
+                             torch.empty((rows, 4 + t), dtype=torch.int32, device=dev),
+                             torch.empty((rows,), dtype=torch.uint8, device=dev))
+        ko, so, do = self._bufs[o]
+        n = C.c_size_t()
+        check(lib().qk_u32_flows_merge_device(ctx.handle, ka.data_ptr(), sa.data_ptr(), self._n, keys.data_ptr(),
+                                              sketches.data_ptr(), nb, t, int(frequency_pkts), ko.data_ptr(),
+                                              so.data_ptr(), do.data_ptr(), ko.shape[0], C.byref(n),
+                                              _flow_stream(ko)), "flows_merge")
+        self._cur, self._n = o, n.value
+        return do[:self._n]
+
+    def insert_packets(self, bufs, stride: int = 67, meta=None, my_addr=None, frequency_pkts: int = 0,
+                       ctx: Context | None = None) -> dict:
+        """Batch of captured records (CUDA uint8 tensor): extract, group by
+        AddrKey and encode per flow on the device, then merge into the table
+        there.  A batch with a Reset replaces the table, as FlowQuacks does.
+        stats["due"] lists the AddrKeys of the flows whose count crossed a
+        multiple of frequency_pkts during the batch
+        (start_sidekick_multi_frequency_pkts, sidekick_multi.rs:274); the quACK
+        to send for them is the end-of-batch one."""
+        ctx = ctx or get_context(self.device)
+        keys, sk, stats = encode_flows(bufs, self.threshold, stride, meta, my_addr, ctx, device_out=True,
+                                       cap=self._batch_cap)
+        # room for the next batch's flows: a batch of more runs twice
+        self._batch_cap = max(1024, keys.shape[0] + keys.shape[0] // 8)
+        if stats["resets"]:
+            self.clear()
+        due = self.merge(keys, sk, frequency_pkts, ctx)
+        stats["due"] = []
+        if frequency_pkts:
+            hit = self.keys[due.bool()].cpu().numpy()
+            stats["due"] = [hit[i].tobytes() for i in range(hit.shape[0])]
+        return stats
+
+    def quacks(self, keys, ctx: Context | None = None) -> list:
+        ctx = ctx or get_context(self.device)
+        return flows_lookup(self.keys, self.sketches, keys, ctx)
+
+    def quack(self, addr_key: bytes, ctx: Context | None = None):
+        return self.quacks([addr_key], ctx)[0]
+
+    def senders(self) -> dict:
+        """The whole table in one D2H copy: {AddrKey: PowerSumQuackU32}."""
+        if not self._n:
+            return {}
+        k = self.keys.cpu().numpy()
+        raw = self.sketches.cpu().numpy().tobytes()
+        rec = 4 * (4 + self.threshold)
+        return {k[i].tobytes(): _quack_from_bytes(raw[i * rec:(i + 1) * rec], self.threshold)
+                for i in range(self._n)}
+
+    def diff(self, peer, ctx: Context | None = None):
+        """media_client.rs:295-296 per flow: this table minus `peer` (another
+        DeviceFlowQuacks or a (keys, sketches) pair), one record per flow of
+        this table in key order — what decode_segments accepts unchanged."""
+        ctx = ctx or get_context(self.device)
+        kb, sb = (peer.keys, peer.sketches) if isinstance(peer, DeviceFlowQuacks) else peer
+        return flows_diff(self.keys, self.sketches, kb, sb, ctx)[0]
 
 
 def partial_words(threshold: int, bits: int = 32) -> int:
