@@ -37,6 +37,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "basis32.h"
 #include "field.h"
 
 namespace qk {
@@ -105,6 +106,17 @@ __device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int m) {
 #define QK_CLOB0 "s40", "s41", "s42", "s43", "s44", "s45", "s46", "s47"
 #define QK_CLOB1 "s48", "s49", "s50", "s51", "s52", "s53", "s54", "s55"
 #define QK_EXPAND(M, ...) M(__VA_ARGS__)
+// pair form (the nine-power basis, below): each multiply-add has its own two
+// operands, acc_j += l_j * r_j
+#define QK_MAC4PS(P0, P1, P2, P3, T)                                                                      \
+    "v_mad_u64_u32 %0, " P0 ", %8, %9, %0\n\t"                                                         \
+    "v_mad_u64_u32 %1, " P1 ", %10, %11, %1\n\t"                                                       \
+    "v_mad_u64_u32 %2, " P2 ", %12, %13, %2\n\t"                                                       \
+    "v_mad_u64_u32 %3, " P3 ", %14, %15, %3\n\t"                                                       \
+    "s_bcnt1_i32_b64 " T ", " P0 "\n\ts_add_u32 %4, %4, " T "\n\t"                                          \
+    "s_bcnt1_i32_b64 " T ", " P1 "\n\ts_add_u32 %5, %5, " T "\n\t"                                          \
+    "s_bcnt1_i32_b64 " T ", " P2 "\n\ts_add_u32 %6, %6, " T "\n\t"                                          \
+    "s_bcnt1_i32_b64 " T ", " P3 "\n\ts_add_u32 %7, %7, " T
 
 // acc_j += A * b_j (64-bit), wraps counted per lane (c_j) or per wave (s_j)
 template <int SET>
@@ -135,6 +147,23 @@ __device__ __forceinline__ void mac4s(uint64_t &a0, uint64_t &a1, uint64_t &a2, 
         asm volatile(QK_EXPAND(QK_MAC4S, QK_SET1T)
             : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+s"(s0), "+s"(s1), "+s"(s2), "+s"(s3)
             : "v"(A), "v"(b0), "v"(b1), "v"(b2), "v"(b3)
+            : "scc", "s57", QK_CLOB1);
+}
+// acc_j += l_j * r_j (64-bit), wraps counted per wave (s_j)
+template <int SET>
+__device__ __forceinline__ void mac4ps(uint64_t &a0, uint64_t &a1, uint64_t &a2, uint64_t &a3, uint32_t &s0,
+                                       uint32_t &s1, uint32_t &s2, uint32_t &s3, uint32_t l0, uint32_t r0,
+                                       uint32_t l1, uint32_t r1, uint32_t l2, uint32_t r2, uint32_t l3,
+                                       uint32_t r3) {
+    if constexpr (SET == 0)
+        asm volatile(QK_EXPAND(QK_MAC4PS, QK_SET0T)
+            : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+s"(s0), "+s"(s1), "+s"(s2), "+s"(s3)
+            : "v"(l0), "v"(r0), "v"(l1), "v"(r1), "v"(l2), "v"(r2), "v"(l3), "v"(r3)
+            : "scc", "s56", QK_CLOB0);
+    else
+        asm volatile(QK_EXPAND(QK_MAC4PS, QK_SET1T)
+            : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+s"(s0), "+s"(s1), "+s"(s2), "+s"(s3)
+            : "v"(l0), "v"(r0), "v"(l1), "v"(r1), "v"(l2), "v"(r2), "v"(l3), "v"(r3)
             : "scc", "s57", QK_CLOB1);
 }
 // lo_j += b_j (32-bit), wraps counted per lane (c_j) or per wave (s_j)
@@ -246,9 +275,14 @@ __device__ __forceinline__ void row2m(uint64_t &a0, uint64_t &a1, uint32_t b0, u
 //  TREE    babies by a product tree (x^(h+l) = x^h x^l, h the highest power
 //          of two below): the same NB - 1 lazy modmuls at dependency depth
 //          log2(NB) instead of NB - 1 (plain passes with min-tracked folds)
+//  BASIS   (CfgBasis) 32 powers from the nine-power basis of basis32.h instead
+//          of the (8, 4) grid: 8 lazy products, 8 direct adds and 24 pair MACs
+//          per id in the same accumulators (slot -> power from the table,
+//          finish())
 template <int NB_, int NA_, int SG_, int ROW0_ = 1, int FOLD_ = 1, bool PAIR_ = false, bool OFF_ = false,
           int XC_ = 0, bool TREE_ = false, int PRIO_ = 0>
 struct Cfg {
+    static constexpr bool BASIS = false;   // CfgBasis (below) sets it
     // PRIO  wave priority (s_setprio) over the accumulation: 4 (the product)
     //       row 0 at 1 and the MAC rows with their scalar wrap counts at 2,
     //       the powers at 0; (measurements) 1 the whole accumulation at 1,
@@ -264,6 +298,14 @@ struct Cfg {
     static constexpr int ROW1 = OFF_ ? 0 : 1;           // group-row number of the first MAC row
     static_assert(NB % 2 == 0 && (NA >= 2 || (OFF_ && NA == 1)), "NB even, NA >= 2 (1: offset pass)");
     static_assert(!OFF_ || FOLD_ == 1, "offset passes use min-tracked folds");
+};
+// The basis form: the plain (8, 4) configuration — its accumulators, every MAC
+// group scalar-counted, row 0 as multiply-adds, min-tracked folds — with the
+// flag set.  A derived type, so that no Cfg<...> instantiation is renamed.
+template <int PRIO_>
+struct CfgBasis : Cfg<8, 4, 8, 1, 1, false, false, 0, false, PRIO_> {
+    static constexpr bool BASIS = true;
+    static_assert(PRIO_ == 0 || PRIO_ == 4, "basis form: no priority change, or the product's two levels");
 };
 
 template <int NB, int NA, int ROWS = NA - 1>
@@ -421,6 +463,47 @@ struct LazyChain {
 QK_CHAINS(4)
 QK_CHAINS(6)
 QK_CHAINS(8)
+
+// ---- the nine-power basis (basis32.h) as one statement ----------------------
+// The same window and rules as LazyChain: Q in v[6:7], each result in the even
+// register of its own pair v[8:9] .. v[22:23] (V[1] .. V[8] in the order of
+// basis32::CHAIN), the odd halves clobbered, carry-outs to s[58:59], the
+// minimum of the eight results formed in the dead v9.  The text below is
+// basis32::CHAIN written out (checked underneath): 2 = 1+1, 3 = 2+1, 6 = 3+3,
+// 8 = 6+2, 12 = 6+6, 16 = 8+8, 13 = 12+1, 15 = 12+3.
+#define QK_BASIS_CHAIN                                                                                 \
+    QK_LP(8, 9, "%[id]", "%[id]")                                                                      \
+    QK_LP(10, 11, "v8", "%[id]")                                                                       \
+    QK_LP(12, 13, "v10", "v10")                                                                        \
+    QK_LP(14, 15, "v12", "v8")                                                                         \
+    QK_LP(16, 17, "v12", "v12")                                                                        \
+    QK_LP(18, 19, "v14", "v14")                                                                        \
+    QK_LP(20, 21, "v16", "%[id]")                                                                      \
+    QK_LP(22, 23, "v16", "v10")                                                                        \
+    "v_min3_u32 v9, v8, v10, v12\n\t"                                                                  \
+    "v_min3_u32 v9, v9, v14, v16\n\t"                                                                  \
+    "v_min3_u32 v9, v9, v18, v20\n\t"                                                                  \
+    "v_min_u32_e32 v9, v9, v22\n\t"
+constexpr bool basis_chain_is(const uint8_t (&t)[3 * basis32::NP]) {
+    for (int i = 0; i < basis32::NP; ++i)
+        if (basis32::CHAIN[i].power != t[3 * i] || basis32::CHAIN[i].left != t[3 * i + 1] ||
+            basis32::CHAIN[i].right != t[3 * i + 2])
+            return false;
+    return true;
+}
+static_assert(basis_chain_is({2, 1, 1, 3, 2, 1, 6, 3, 3, 8, 6, 2, 12, 6, 6, 16, 8, 8, 13, 12, 1, 15, 12, 3}),
+              "QK_BASIS_CHAIN is basis32::CHAIN written out");
+// V[0] = id, V[i + 1] = the chain's step i (lazy); returns their minimum
+__device__ __forceinline__ uint32_t basis_chain(uint32_t id, uint32_t (&V)[basis32::NE]) {
+    uint32_t mn;
+    V[0] = id;
+    asm(QK_BASIS_CHAIN
+        : "=&{v9}"(mn), "=&{v8}"(V[1]), "=&{v10}"(V[2]), "=&{v12}"(V[3]), "=&{v14}"(V[4]), "=&{v16}"(V[5]),
+          "=&{v18}"(V[6]), "=&{v20}"(V[7]), "=&{v22}"(V[8])
+        : [id] "v"(id)
+        : "v6", "v7", "v11", "v13", "v15", "v17", "v19", "v21", "v23", "s58", "s59");
+    return mn;
+}
 
 // powers of one id; returns a value below WRAP_BELOW if a lazy fold may have
 // wrapped (the caller then recomputes exactly): the minimum of the products
@@ -583,6 +666,44 @@ __device__ __forceinline__ void accumulate(Acc<C::NB, C::NA, C::ROWS> &S, const 
     }
 }
 
+// The basis form's accumulation, in the grid form's shape: two groups of four direct
+// adds (the x1 form, priority 1), then six groups of four pair MACs whose
+// wraps are counted on the scalar unit (priority 2), alternating SGPR sets.
+// Direct accumulator i is S.r0[i], pair accumulator i is S.m[i / 8][i % 8];
+// their powers are basis32::DIRECT[i] and basis32::MAC[i] (finish()).
+template <class C, int G>
+__device__ __forceinline__ void basis_direct4(Acc<8, 4, 3> &S, const uint32_t (&V)[basis32::NE]) {
+    constexpr int i = 4 * G;
+    row4m<G % 2>(S.r0[i], S.r0[i + 1], S.r0[i + 2], S.r0[i + 3], V[basis32::direct_v(i)],
+                 V[basis32::direct_v(i + 1)], V[basis32::direct_v(i + 2)], V[basis32::direct_v(i + 3)]);
+}
+template <class C, int G>
+__device__ __forceinline__ void basis_mac4(Acc<8, 4, 3> &S, const uint32_t (&V)[basis32::NE]) {
+    constexpr int i = 4 * G, a = i / 8, b = i % 8;
+    static_assert(scalar_group<C>(a + 1, b), "basis form: pair MACs are scalar-counted");
+    mac4ps<G % 2>(S.m[a][b], S.m[a][b + 1], S.m[a][b + 2], S.m[a][b + 3], S.c[a][b], S.c[a][b + 1], S.c[a][b + 2],
+                  S.c[a][b + 3], V[basis32::mac_l(i)], V[basis32::mac_r(i)], V[basis32::mac_l(i + 1)],
+                  V[basis32::mac_r(i + 1)], V[basis32::mac_l(i + 2)], V[basis32::mac_r(i + 2)],
+                  V[basis32::mac_l(i + 3)], V[basis32::mac_r(i + 3)]);
+}
+template <class C>
+__device__ __forceinline__ void accumulate_basis(Acc<8, 4, 3> &S, const uint32_t (&V)[basis32::NE]) {
+    static_assert(basis32::ND == 8 && basis32::NM == 24, "two direct groups, six pair groups");
+    basis_direct4<C, 0>(S, V);
+    basis_direct4<C, 1>(S, V);
+    if constexpr (C::PRIO == 4) __builtin_amdgcn_s_setprio(2);
+    basis_mac4<C, 0>(S, V);
+    basis_mac4<C, 1>(S, V);
+    basis_mac4<C, 2>(S, V);
+    basis_mac4<C, 3>(S, V);
+    basis_mac4<C, 4>(S, V);
+    basis_mac4<C, 5>(S, V);
+}
+// the power (1..32) held by the accumulator that finish() numbers (a, b)
+constexpr int basis_slot_power(int a, int b) {
+    return a == 0 ? basis32::DIRECT[b] : basis32::MAC[(a - 1) * 8 + b];
+}
+
 // wave priority around an id's accumulation (Cfg PRIO; accumulate raises it
 // further before the MAC rows for PRIO 3-6)
 template <class C> __device__ __forceinline__ void prio_enter() {
@@ -600,6 +721,19 @@ template <class C> __device__ __forceinline__ void prio_exit() {
 template <class C>
 __device__ __forceinline__ void one(Acc<C::NB, C::NA, C::ROWS> &S, uint32_t id, uint32_t base = 0, uint32_t xb = 0,
                                     uint32_t *xnext = nullptr) {
+    if constexpr (C::BASIS) {   // the same steps over the basis's nine values
+        uint32_t V[basis32::NE];
+        const uint32_t mn = basis_chain(id, V);
+        prio_enter<C>();
+        if constexpr (C::PRIO != 0) __builtin_amdgcn_sched_barrier(0);
+        const bool w = mn < WRAP_BELOW;
+        if (__builtin_expect(__any(w), 0)) {
+            if (w) basis32::chain_exact(id, V);
+        }
+        accumulate_basis<C>(S, V);
+        prio_exit<C>();
+        return;
+    }
     uint32_t B[C::NB], A[C::ROWS];
     const uint32_t mn = powers<C>(id, B, A, base, xb, xnext);
     // the priority change sits between the chain and the wrap check that reads
@@ -680,7 +814,9 @@ __device__ __forceinline__ void finish(const Acc<C::NB, C::NA, C::ROWS> &S, uint
             x = fold64_32(x);                                                         // < 2^32
 #pragma unroll
             for (int off = 32; off >= 1; off >>= 1) x += shfl_xor_u64(x, off);        // < 2^38
-            if (lane == 0) sm[wave * (NB * NA) + a * NB + b] = x;
+            // sm is indexed by power - 1: the grid's a * NB + b, the basis's from its table
+            const int m = C::BASIS ? basis_slot_power(a, b) - 1 : a * NB + b;
+            if (lane == 0) sm[wave * (NB * NA) + m] = x;
         }
     }
     __syncthreads();

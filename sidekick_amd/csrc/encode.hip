@@ -25,6 +25,11 @@
 //     anchor at the bench run's own shader clock (bench.py roofline.valu,
 //     DESIGN.md §4) and ~0.20-0.21 of the HBM read roofline (4 B/id; the
 //     line moves with the box's shader clock, 2.0-2.1 GHz).
+//   * t = 31..32 (u32) — k_encode_u32_basis / k_encode_u32_basis_dyn (knob
+//     u32_basis, default 1): the same kernel bodies with the 32 powers from
+//     the nine-power basis of basis32.h, 8 lazy modmuls per id instead of the
+//     (8, 4) grid's 9 (bsgs.h CfgBasis).  u32_basis = 0 and the all-VALU
+//     fallback take the grid.
 //   * 14 <= t <= 80 (u64) — k_encode_u64_bsgs<NA,SG,F> (bsgs64.h): the
 //     same split with the babies/giants of a 256-id tile shared through LDS,
 //     each wave owning two babies' MAC rows (paired, at raised priority).
@@ -132,6 +137,23 @@ __global__ __launch_bounds__(BLOCK, (NB * NA == 32 ? 5 : NB * NA > 64 ? 2 : NB *
     const bsgs::DynArgs da) {
     bsgs::body_dyn<bsgs::Cfg<NB, NA, SG, QK_BSGS_ROW0, QK_BSGS_FOLD, false, false, 0, false, PRIO ? 4 : 0>>(
         ids, n, head, T, partials, da);
+}
+
+// t = 31..32 from the nine-power basis (basis32.h, bsgs.h CfgBasis; knob
+// u32_basis): 8 lazy products per id instead of the (8,4) grid's 9, the same
+// accumulators, wrap counting and priorities.  Static and dynamic form.
+template <int PRIO = 1>
+__global__ __launch_bounds__(BLOCK, 5) void k_encode_u32_basis(const uint32_t *__restrict__ ids, uint64_t n,
+                                                              uint32_t head, uint32_t T,
+                                                              uint64_t *__restrict__ partials) {
+    bsgs::body<bsgs::CfgBasis<PRIO ? 4 : 0>>(ids, n, head, T, partials);
+}
+template <int PRIO = 1>
+__global__ __launch_bounds__(BLOCK, 5) void k_encode_u32_basis_dyn(const uint32_t *__restrict__ ids, uint64_t n,
+                                                                  uint32_t head, uint32_t T,
+                                                                  uint64_t *__restrict__ partials,
+                                                                  const bsgs::DynArgs da) {
+    bsgs::body_dyn<bsgs::CfgBasis<PRIO ? 4 : 0>>(ids, n, head, T, partials, da);
 }
 
 // Pass 0 of a multi-pass encode (powers 1..80) that also writes x^80 per id
@@ -1090,6 +1112,11 @@ static int enc32(qk_ctx *ctx, const uint32_t *ids, size_t n, uint32_t T, uint64_
         if (T >= 21 && T <= 24) return QK_BSGS(4, 6, 6);
         if (T >= 25 && T <= 28) return QK_BSGS(4, 7, 7);
         if (T >= 29 && T <= 30) return QK_BSGS(6, 5, 5);
+        if (T >= 31 && T <= 32 && ctx->knobs.u32_basis != 0)   // the nine-power basis (basis32.h)
+            return dyn ? run_encode_dyn(ctx, k_encode_u32_basis_dyn<1>, k_finalize_u32, 32, ids, n, head, T, out, acc,
+                                        s)
+                       : run_encode<uint32_t>(ctx, k_encode_u32_basis<1>, k_finalize_u32, 32, 1, ids, n, head, T,
+                                              (n + 3) / 4, BLOCK, out, acc, s, 0);
         if (T >= 31 && T <= 32) return QK_BSGS(8, 4, QK_BSGS_SG_T32);
         if (T >= 33 && T <= 36) return QK_BSGS(6, 6, 6);
         if (T >= 37 && T <= 40) return QK_BSGS(8, 5, 10);
