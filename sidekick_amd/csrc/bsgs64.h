@@ -37,8 +37,8 @@
 namespace qk {
 namespace bsgs64 {
 
-constexpr int BLOCK = 256;
-constexpr int WAVES = BLOCK / 64;
+using bsgs::BLOCK;   // kernels name bsgs64::BLOCK in their launch bounds
+using bsgs::WAVES;
 constexpr int NB = 8;
 
 // V <- V * x mod p, V and the result < 2^64 (not necessarily canonical),

@@ -7,7 +7,7 @@
 //
 // Kernels and dispatch (`enc32` / `enc64` below):
 //   * 5 <= t <= 80 (u32) — the headline kernel k_encode_u32_bsgs<NB,NA,SG>
-//     (bsgs.h): baby steps x^1..x^NB and giant steps x^(NB a) per id, lane
+//     (bsgs.h; the shape of each threshold: QK_U32_SHAPES below): baby steps x^1..x^NB and giant steps x^(NB a) per id, lane
 //     private, then S_(NB a + b) += A_a * B_b as 64-bit multiply-accumulates
 //     whose wraps are counted per wave on the scalar unit.  t = 32 is
 //     (NB, NA) = (8, 4): 9 lazy modmuls + 24 MACs + 8 row-0 mads per id =
@@ -44,6 +44,10 @@
 // Integer-issue bound; no MFMA (north_star).  (The int8 matrix-core variant
 // measured in rounds 2-3, DESIGN.md §3.9, was removed from the sources in
 // round 4; it lives in the git history.)
+#include <algorithm>
+#include <type_traits>
+#include <utility>
+
 #include "ctx.h"
 #include "field.h"
 #include "bsgs.h"
@@ -64,14 +68,9 @@ namespace qk {
 
 QK_WARM_KERNEL(encode)
 
-constexpr int BLOCK = 256;
-constexpr int WAVES = BLOCK / 64;
-
-__device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int m) {
-    const uint32_t lo = __shfl_xor((int)(uint32_t)v, m, 64);
-    const uint32_t hi = __shfl_xor((int)(uint32_t)(v >> 32), m, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
+using bsgs::BLOCK;
+using bsgs::WAVES;
+using bsgs::shfl_xor_u64;
 
 // ------------------------------------------------------------------ u32
 // Power chain in t-form (field.h: tstep32): per power three v_mad_u64_u32,
@@ -112,7 +111,7 @@ __device__ __forceinline__ void chain32x4(uint64_t (&acc)[K], uint4 w) {
     }
 }
 
-// ---- baby-step / giant-step encode for 9 <= t <= 32 (bsgs.h)
+// ---- baby-step / giant-step encode, the shapes of QK_U32_SHAPES below (bsgs.h)
 // waves per SIMD the register budget is sized for (tools/tune_bsgs.hip: 5 for
 // (8,4) beat 4 by 2-3 %; its three spilled VGPRs live outside the loop)
 // PRIO (knob bsgs_prio): wave priority over each id's accumulation — row 0
@@ -157,7 +156,7 @@ __global__ __launch_bounds__(BLOCK, 5) void k_encode_u32_basis_dyn(const uint32_
 }
 
 // Pass 0 of a multi-pass encode (powers 1..80) that also writes x^80 per id
-// for pass 1 (the x^base cache, enc32_passes)
+// for pass 1 (the x^base cache, enc_passes_chunk)
 template <int SG, int PRIO = 1>
 __global__ __launch_bounds__(BLOCK, 2) void k_encode_u32_bsgs_x80(const uint32_t *__restrict__ ids, uint64_t n,
                                                                  uint32_t head, uint32_t T,
@@ -268,46 +267,20 @@ __global__ __launch_bounds__(BLOCK) void k_encode_u32_gn(const uint32_t *__restr
     block_store<G, K>(acc, T, partials, sm, Fold32{});
 }
 
-// Sum block partials of power m = blockIdx.x; write canonical S_m (or add it
-// into out when accumulate), count and last id.
+// Sum block partials of power m = blockIdx.x; write canonical S_m to out[m]
+// (or add it in when accumulate).  The launch with meta != nullptr also
+// writes count and last id there (meta[0], meta[1]): out + T for a single-pass
+// encode; in a multi-pass encode out is the partial vector + the pass's base
+// and only pass 0 has a meta.
 __global__ __launch_bounds__(BLOCK) void k_finalize_u32(const uint64_t *__restrict__ partials,
                                                         uint32_t nblocks, uint32_t T,
                                                         const uint32_t *__restrict__ ids, uint64_t n,
-                                                        uint64_t *__restrict__ out, int accumulate) {
+                                                        uint64_t *__restrict__ out,
+                                                        uint64_t *__restrict__ meta, int accumulate) {
     __shared__ uint64_t sm[WAVES];
     const uint32_t m = blockIdx.x;
     uint64_t s = 0;
     for (uint32_t b = threadIdx.x; b < nblocks; b += BLOCK) s += partials[(size_t)m * nblocks + b]; // < 2^60
-    s = fold64_32(s);
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) s += shfl_xor_u64(s, off);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint64_t tot = 0;
-        for (int w = 0; w < WAVES; ++w) tot += sm[w];
-        uint32_t c = canon32(fold64_32(tot));
-        out[m] = accumulate ? (uint64_t)add32((uint32_t)out[m], c) : (uint64_t)c;
-        if (m == 0) {
-            out[T] = accumulate ? out[T] + n : n;
-            if (n) out[T + 1] = ids[n - 1];
-            else if (!accumulate) out[T + 1] = 0;
-        }
-    }
-}
-
-// One pass of a multi-pass encode: powers m < T of this pass go to
-// out[m] (out = the partial vector + the pass's base); the pass with
-// meta != nullptr also writes count and last id there (meta[0], meta[1]).
-__global__ __launch_bounds__(BLOCK) void k_finalize_u32_pass(const uint64_t *__restrict__ partials,
-                                                             uint32_t nblocks, uint32_t T,
-                                                             const uint32_t *__restrict__ ids, uint64_t n,
-                                                             uint64_t *__restrict__ out,
-                                                             uint64_t *__restrict__ meta, int accumulate) {
-    __shared__ uint64_t sm[WAVES];
-    const uint32_t m = blockIdx.x;
-    uint64_t s = 0;
-    for (uint32_t b = threadIdx.x; b < nblocks; b += BLOCK) s += partials[(size_t)m * nblocks + b];
     s = fold64_32(s);
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) s += shfl_xor_u64(s, off);
@@ -537,11 +510,13 @@ __global__ __launch_bounds__(BLOCK) void k_encode_u64_gn(const uint64_t *__restr
 
 // Sum block limb partials of power m = blockIdx.x; write canonical S_m as
 // two 32-bit limbs out[2m], out[2m+1] (or add it in when accumulate); the
-// launch with meta != nullptr also writes count and last id (meta[0..1]).
-__device__ __forceinline__ void finalize_u64_body(const uint64_t *__restrict__ partials, uint32_t nblocks,
-                                                  uint32_t T, const uint64_t *__restrict__ ids, uint64_t n,
-                                                  uint64_t *__restrict__ out, uint64_t *__restrict__ meta,
-                                                  int accumulate) {
+// launch with meta != nullptr also writes count and last id (meta[0..1]):
+// out + 2 T for a single-pass encode, pass 0 alone in a multi-pass one.
+__global__ __launch_bounds__(BLOCK) void k_finalize_u64(const uint64_t *__restrict__ partials,
+                                                        uint32_t nblocks, uint32_t T,
+                                                        const uint64_t *__restrict__ ids, uint64_t n,
+                                                        uint64_t *__restrict__ out,
+                                                        uint64_t *__restrict__ meta, int accumulate) {
     __shared__ uint64_t sm[2][WAVES];
     const uint32_t m = blockIdx.x; // power index
     uint64_t a = 0, b = 0;         // limb sums, each < nblocks * 2^40
@@ -577,22 +552,6 @@ __device__ __forceinline__ void finalize_u64_body(const uint64_t *__restrict__ p
             else if (!accumulate) meta[1] = 0;
         }
     }
-}
-
-__global__ __launch_bounds__(BLOCK) void k_finalize_u64_pass(const uint64_t *__restrict__ partials,
-                                                             uint32_t nblocks, uint32_t T,
-                                                             const uint64_t *__restrict__ ids, uint64_t n,
-                                                             uint64_t *__restrict__ out,
-                                                             uint64_t *__restrict__ meta, int accumulate) {
-    finalize_u64_body(partials, nblocks, T, ids, n, out, meta, accumulate);
-}
-
-// single-pass form: count and last id right after the T limb pairs
-__global__ __launch_bounds__(BLOCK) void k_finalize_u64(const uint64_t *__restrict__ partials,
-                                                        uint32_t nblocks, uint32_t T,
-                                                        const uint64_t *__restrict__ ids, uint64_t n,
-                                                        uint64_t *__restrict__ out, int accumulate) {
-    finalize_u64_body(partials, nblocks, T, ids, n, out, out + 2 * T, accumulate);
 }
 
 // u64 baby-step / giant-step (bsgs64.h): 256-id tiles, babies and giants
@@ -650,11 +609,34 @@ __global__ __launch_bounds__(bsgs64::BLOCK, 4) void k_encode_u64_bsgs_off(const 
 }
 
 // ------------------------------------------------------------- dispatch
+template <int... Vs>
+using ints = std::integer_sequence<int, Vs...>;
+
+// A runtime integer as a template argument: f(std::integral_constant<int, V>)
+// for the V of Vs equal to v, `none` when there is no such V.
+template <int... Vs, class F>
+static int with_int(int v, ints<Vs...>, int none, F &&f) {
+    int rc = none;
+    (void)((v == Vs && ((rc = f(std::integral_constant<int, Vs>{})), true)) || ...);
+    return rc;
+}
+
+// units / per_block workgroups, at most `mult` rounds of the resident ones
+// (mult <= 0: knob grid_mult), or the override.
+static uint32_t grid_clamp(const qk_ctx *ctx, uint64_t units, uint32_t per_block, uint64_t blocks_per_cu, int mult) {
+    if (ctx->grid_override) return ctx->grid_override;
+    const uint64_t full = (uint64_t)ctx->num_cus * blocks_per_cu * (uint64_t)(mult > 0 ? mult : ctx->knobs.grid_mult);
+    uint64_t need = (units + per_block - 1) / per_block;
+    if (need < 1) need = 1;
+    return (uint32_t)(need < full ? need : full);
+}
+
 template <typename KernelT>
 static uint32_t grid_for(qk_ctx *ctx, KernelT kern, uint64_t units, uint32_t per_block, int mult = 0) {
-    if (ctx->grid_override) return ctx->grid_override;
     int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, BLOCK, 0) != hipSuccess || occ < 1) occ = 1;
+    if (ctx->grid_override || hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, BLOCK, 0) != hipSuccess ||
+        occ < 1)
+        occ = 1;
     // knob grid_mult: resident workgroups x this.  The static encode kernels
     // (the u64 kernels, the chains, the u32 BSGS kernels at enc_dyn = 0 or
     // n >= 2^32) split the ids evenly over the grid; with one round of
@@ -663,10 +645,7 @@ static uint32_t grid_for(qk_ctx *ctx, KernelT kern, uint64_t units, uint32_t per
     // later workgroups (the dynamic form asks for one round: mult = 1)
     // (mult > 0: fixed by the caller — u32 t > 48 and the u32 passes measured
     // 0.4-2.3 % slower at three rounds, profiles/r04/grid_mult/)
-    const uint64_t full = (uint64_t)ctx->num_cus * (uint64_t)occ * (uint64_t)(mult > 0 ? mult : ctx->knobs.grid_mult);
-    uint64_t need = (units + per_block - 1) / per_block;
-    if (need < 1) need = 1;
-    return (uint32_t)(need < full ? need : full);
+    return grid_clamp(ctx, units, per_block, (uint64_t)occ, mult);
 }
 
 // An upper bound on grid_for over every kernel a multi-pass encode may
@@ -675,34 +654,57 @@ static uint32_t grid_for(qk_ctx *ctx, KernelT kern, uint64_t units, uint32_t per
 // in workgroups of BLOCK threads.  The x^base cache is placed after the
 // largest partials this allows.
 static uint32_t grid_cap(const qk_ctx *ctx, uint64_t units, uint32_t per_block, int mult = 0) {
-    if (ctx->grid_override) return ctx->grid_override;
-    const uint64_t full = (uint64_t)ctx->num_cus * (uint64_t)ctx->max_blocks_per_cu(BLOCK) *
-                          (uint64_t)(mult > 0 ? mult : ctx->knobs.grid_mult);
-    uint64_t need = (units + per_block - 1) / per_block;
-    if (need < 1) need = 1;
-    return (uint32_t)(need < full ? need : full);
+    return grid_clamp(ctx, units, per_block, ctx->max_blocks_per_cu(BLOCK), mult);
 }
 
-// Launch main kernel (+profiling events) then finalize.
-template <typename IdT, typename KernelT, typename FinT>
-static int run_encode(qk_ctx *ctx, KernelT kern, FinT fin, uint32_t GK, uint32_t words_per_power,
-                      const IdT *d_ids, size_t n, uint32_t head, uint32_t T, uint64_t units,
-                      uint32_t per_block, uint64_t *d_partial, int accumulate, hipStream_t s, int mult = 0) {
-    const uint32_t nb = grid_for(ctx, kern, units, per_block, mult);
-    const size_t need = (size_t)nb * words_per_power * GK * sizeof(uint64_t);
-    int rc = ensure_scratch(ctx, need, s);
-    if (rc) return rc;
+template <class KernelT, class... Args>
+static void launch(KernelT kern, uint32_t nb, hipStream_t s, Args... args) {
+    hipLaunchKernelGGL(kern, dim3(nb), dim3(BLOCK), 0, s, args...);
+}
+
+// The launch sequence of every encode: room for the partials of nb
+// workgroups, the scratch hand-off, main(nb, partials) — the main kernel,
+// between the profiling events — then fin(nb, partials), the finalize.
+template <class Main, class Fin>
+static int launch_encode(qk_ctx *ctx, uint32_t nb, size_t scratch_bytes, hipStream_t s, Main &&main, Fin &&fin) {
+    if (int rc = ensure_scratch(ctx, scratch_bytes, s)) return rc;
     uint64_t *partials = (uint64_t *)ctx->d_scratch;
-    rc = scratch_acquire(ctx, s);
-    if (rc) return rc;
+    if (int rc = scratch_acquire(ctx, s)) return rc;
     hipEvent_t e0 = prof_begin(ctx, s);
-    hipLaunchKernelGGL(kern, dim3(nb), dim3(BLOCK), 0, s, d_ids, (uint64_t)n, head, T, partials);
+    main(nb, partials);
     prof_end(ctx, s, e0);
     QK_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(fin, dim3(T), dim3(BLOCK), 0, s, partials, nb, T, d_ids, (uint64_t)n, d_partial,
-                       accumulate);
+    fin(nb, partials);
     QK_HIP_TRY(hipGetLastError());
     return scratch_release(ctx, s);
+}
+
+// The finalize of T powers into out, count and last id into meta (nullptr:
+// not written; out + T words of a single-pass encode), as launch_encode's fin.
+template <typename IdT>
+static auto finalize_to(uint32_t T, const IdT *ids, size_t n, uint64_t *out, uint64_t *meta, int acc, hipStream_t s) {
+    return [=](uint32_t nb, const uint64_t *partials) {
+        if constexpr (sizeof(IdT) == 4)
+            hipLaunchKernelGGL(k_finalize_u32, dim3(T), dim3(BLOCK), 0, s, partials, nb, T, ids, (uint64_t)n, out, meta,
+                               acc);
+        else
+            hipLaunchKernelGGL(k_finalize_u64, dim3(T), dim3(BLOCK), 0, s, partials, nb, T, ids, (uint64_t)n, out, meta,
+                               acc);
+    };
+}
+
+// A single-pass encode with a kernel of the plain form (ids, n, head, T,
+// partials) that keeps GK partial rows per workgroup.
+template <typename IdT, typename KernelT>
+static int run_encode(qk_ctx *ctx, KernelT kern, uint32_t GK, const IdT *d_ids, size_t n, uint32_t head, uint32_t T,
+                      uint64_t units, uint32_t per_block, uint64_t *d_partial, int accumulate, hipStream_t s,
+                      int mult = 0) {
+    constexpr uint32_t W = sizeof(IdT) / 4;   // 32-bit limbs, each a partial row and an output word, per power
+    const uint32_t nb = grid_for(ctx, kern, units, per_block, mult);
+    return launch_encode(
+        ctx, nb, (size_t)nb * W * GK * sizeof(uint64_t), s,
+        [&](uint32_t, uint64_t *partials) { launch(kern, nb, s, d_ids, (uint64_t)n, head, T, partials); },
+        finalize_to(T, d_ids, n, d_partial, d_partial + W * T, accumulate, s));
 }
 
 // The dynamic form of a single-pass u32 BSGS encode (bsgs.h body_dyn): one
@@ -711,44 +713,36 @@ static int run_encode(qk_ctx *ctx, KernelT kern, FinT fin, uint32_t GK, uint32_t
 // The counters are never reset: a launch of nb workgroups moves each by its
 // region's chunks + nb * WAVES (every wave ends with one failed claim at
 // every counter), and the context keeps their values for the next launch's
-// bases.  Launches are ordered by the scratch hand-off (scratch_acquire /
-// scratch_release), so a launch finds the counters at its bases whatever
-// stream it runs on.
+// bases.  Launches are ordered by the scratch hand-off (launch_encode), so a
+// launch finds the counters at its bases whatever stream it runs on.
 static_assert((size_t)bsgs::DYN_NCTR * bsgs::DYN_CTR_STRIDE <= ENC_CLAIM_WORDS &&
                   bsgs::DYN_NCTR == sizeof(qk_ctx::enc_claim_base) / sizeof(uint64_t),
               "ctx.h: room for the dynamic encode's counters and their bases");
-template <typename KernelT, typename FinT>
-static int run_encode_dyn(qk_ctx *ctx, KernelT kern, FinT fin, uint32_t GK, const uint32_t *d_ids, size_t n,
-                          uint32_t head, uint32_t T, uint64_t *d_partial, int accumulate, hipStream_t s) {
+template <typename KernelT>
+static int run_encode_dyn(qk_ctx *ctx, KernelT kern, uint32_t GK, const uint32_t *d_ids, size_t n, uint32_t head,
+                          uint32_t T, uint64_t *d_partial, int accumulate, hipStream_t s) {
     const uint32_t nb = grid_for(ctx, kern, ((uint64_t)n + 3) / 4, BLOCK, 1);
-    int rc = ensure_scratch(ctx, (size_t)nb * GK * sizeof(uint64_t), s);
-    if (rc) return rc;
-    uint64_t *partials = (uint64_t *)ctx->d_scratch;
-    rc = scratch_acquire(ctx, s);
-    if (rc) return rc;
     const uint64_t h = head < n ? head : n;
     const uint64_t nchunks = ((n - h) >> 2) / bsgs::DYN_GROUPS;
     bsgs::DynArgs da;
     da.ctr = (unsigned long long *)(ctx->d_small + ENC_CLAIM);
     da.region = (nchunks + bsgs::DYN_NCTR - 1) / bsgs::DYN_NCTR;
     for (int k = 0; k < bsgs::DYN_NCTR; ++k) da.base[k] = ctx->enc_claim_base[k];
-    hipEvent_t e0 = prof_begin(ctx, s);
-    hipLaunchKernelGGL(kern, dim3(nb), dim3(BLOCK), 0, s, d_ids, (uint64_t)n, head, T, partials, da);
-    prof_end(ctx, s, e0);
-    QK_HIP_TRY(hipGetLastError());
-    for (int k = 0; k < bsgs::DYN_NCTR; ++k)
-        ctx->enc_claim_base[k] += bsgs::dyn_region_len(nchunks, da.region, (uint32_t)k) + (uint64_t)nb * WAVES;
-    hipLaunchKernelGGL(fin, dim3(T), dim3(BLOCK), 0, s, partials, nb, T, d_ids, (uint64_t)n, d_partial,
-                       accumulate);
-    QK_HIP_TRY(hipGetLastError());
-    return scratch_release(ctx, s);
+    auto fin = finalize_to(T, d_ids, n, d_partial, d_partial + T, accumulate, s);
+    return launch_encode(
+        ctx, nb, (size_t)nb * GK * sizeof(uint64_t), s,
+        [&](uint32_t, uint64_t *partials) { launch(kern, nb, s, d_ids, (uint64_t)n, head, T, partials, da); },
+        [&](uint32_t, const uint64_t *partials) {   // the main kernel is enqueued: its claims move the counters
+            for (int k = 0; k < bsgs::DYN_NCTR; ++k)
+                ctx->enc_claim_base[k] += bsgs::dyn_region_len(nchunks, da.region, (uint32_t)k) + (uint64_t)nb * WAVES;
+            fin(nb, partials);
+        });
 }
 
 // sums of per-block partials [power][block] -> canonical S_1..S_T in out[0..T)
 int launch_finalize_powers_u32(const uint64_t *partials, uint32_t nblocks, uint32_t T, uint64_t *out,
                                hipStream_t s) {
-    hipLaunchKernelGGL(k_finalize_u32_pass, dim3(T), dim3(BLOCK), 0, s, partials, nblocks, T,
-                       (const uint32_t *)nullptr, (uint64_t)0, out, (uint64_t *)nullptr, 0);
+    finalize_to(T, (const uint32_t *)nullptr, 0, out, nullptr, 0, s)(nblocks, partials);
     return hipGetLastError() == hipSuccess ? QK_OK : QK_E_HIP;
 }
 
@@ -756,38 +750,8 @@ int launch_finalize_powers_u32(const uint64_t *partials, uint32_t nblocks, uint3
 // kernel (powers 1..80), each further pass the offset kernel with giants
 // from x^base (the ids are read once per pass; HBM has the bandwidth, the
 // passes are integer-issue bound like the single-pass kernels).
-// xcache (offset passes): the per-id x^base cache (xin / xout), placed in
-// the scratch after the partials (run_pass32_cached sizes the scratch once)
-// KIND 0: a plain kernel (ids, n, head, T, partials); 1: an offset pass
-// (+ base, xin, xout); 2: a plain kernel that writes the x^base cache
-// (+ xin, xout)
-template <int KIND, class KernelT>
-static int run_pass(qk_ctx *ctx, KernelT kern, uint32_t GK, const uint32_t *d_ids, size_t n,
-                    uint32_t head, uint32_t Tp, uint32_t base, uint64_t *out, uint64_t *meta, int acc,
-                    hipStream_t s, const uint32_t *xin = nullptr, uint32_t *xout = nullptr) {
-    const uint32_t nb = grid_for(ctx, kern, (n + 3) / 4, BLOCK, 1);
-    if (int rc = ensure_scratch(ctx, (size_t)nb * GK * sizeof(uint64_t), s)) return rc;
-    uint64_t *partials = (uint64_t *)ctx->d_scratch;
-    if (int rc = scratch_acquire(ctx, s)) return rc;
-    hipEvent_t e0 = prof_begin(ctx, s);
-    if constexpr (KIND == 1)
-        hipLaunchKernelGGL(kern, dim3(nb), dim3(BLOCK), 0, s, d_ids, (uint64_t)n, head, Tp, base, partials, xin,
-                           xout);
-    else if constexpr (KIND == 2)
-        hipLaunchKernelGGL(kern, dim3(nb), dim3(BLOCK), 0, s, d_ids, (uint64_t)n, head, Tp, partials, xin, xout);
-    else
-        hipLaunchKernelGGL(kern, dim3(nb), dim3(BLOCK), 0, s, d_ids, (uint64_t)n, head, Tp, partials);
-    prof_end(ctx, s, e0);
-    QK_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_finalize_u32_pass, dim3(Tp), dim3(BLOCK), 0, s, partials, nb, Tp, d_ids, (uint64_t)n, out,
-                       meta, acc);
-    QK_HIP_TRY(hipGetLastError());
-    return scratch_release(ctx, s);
-}
-
-
-static int enc32_passes_chunk(qk_ctx *ctx, const uint32_t *ids, size_t n, uint32_t head, uint32_t T, uint64_t *out,
-                              int acc, hipStream_t s) {
+static int enc_passes_chunk(qk_ctx *ctx, const uint32_t *ids, size_t n, uint32_t head, uint32_t T, uint64_t *out,
+                            int acc, hipStream_t s) {
     // pass 0: powers 1..80 with the single-pass (8,10) kernel; then passes of
     // <= 48 powers with the offset (8,6) kernel (142 VGPRs, 3 waves/SIMD;
     // every row of an offset pass is a MAC row: the 80-power form spills, a
@@ -812,60 +776,46 @@ static int enc32_passes_chunk(qk_ctx *ctx, const uint32_t *ids, size_t n, uint32
     uint32_t pass = 0;
     for (uint32_t base = 0; base < T; ++pass) {
         const uint32_t Tp = std::min<uint32_t>(base == 0 ? 80 : 48, T - base);
-        uint64_t *meta = base == 0 ? out + T : nullptr;
+        // one pass: main(nb, partials) launches kern (GK partial rows per
+        // workgroup); its powers go to out + base, count and last id with pass 0
+        auto run_pass = [&](auto kern, uint32_t GK, auto main) {
+            const uint32_t nb = grid_for(ctx, kern, (n + 3) / 4, BLOCK, 1);
+            return launch_encode(ctx, nb, (size_t)nb * GK * sizeof(uint64_t), s, main,
+                                 finalize_to(Tp, ids, n, out + base, base == 0 ? out + T : nullptr, acc, s));
+        };
+        // an offset pass of NA giant rows; XC: x^base from the cache (bit 0),
+        // x^(base + 8 NA) to it (bit 1)
+        auto off = [&](auto na, auto x) {
+            constexpr int NA = decltype(na)::value, XC = decltype(x)::value;
+            auto kern = k_encode_u32_bsgs_off<NA, 2 * NA, XC, 1>;
+            return run_pass(kern, 8 * NA, [&](uint32_t nb, uint64_t *partials) {
+                launch(kern, nb, s, ids, (uint64_t)n, head, Tp, base, partials, (const uint32_t *)(XC & 1 ? xc : nullptr),
+                       XC & 2 ? xc : nullptr);
+            });
+        };
         // XC: pass 0 writes the cache, the middle passes read and write it, the last reads it
         const int xcm = !xc ? 0 : (pass > 0 ? 1 : 0) | (pass < npass ? 2 : 0);
         int rc;
-        if (base == 0 && xc)
-            rc = run_pass<2>(ctx, k_encode_u32_bsgs_x80<16, 1>, 80, ids, n, head, Tp, 0, out, meta, acc, s, nullptr,
-                             xc);
-        else if (base == 0)
-            rc = run_pass<0>(ctx, k_encode_u32_bsgs<8, 10, 16, 1>, 80, ids, n, head, Tp, 0, out, meta, acc, s);
-        else if (Tp <= 40) {   // the last pass (npass >= 1): NA = ceil(Tp / 8) giant rows
-#define QK_OFF32(NA_, XC_) k_encode_u32_bsgs_off<NA_, 2 * NA_, XC_, 1>
-#define QK_LAST32(NA_)                                                                                       \
-    (xcm & 1 ? run_pass<1>(ctx, QK_OFF32(NA_, 1), 8 * NA_, ids, n, head, Tp, base,                            \
-                              out + base, meta, acc, s, xc, nullptr)                                          \
-             : run_pass<1>(ctx, QK_OFF32(NA_, 0), 8 * NA_, ids, n, head, Tp, base,                            \
-                              out + base, meta, acc, s))
-            switch ((Tp + 7) / 8) {
-            case 1: rc = QK_LAST32(1); break;   // <= 8 powers: one giant row (x^base)
-            case 2: rc = QK_LAST32(2); break;
-            case 3: rc = QK_LAST32(3); break;
-            case 4: rc = QK_LAST32(4); break;
-            default: rc = QK_LAST32(5); break;
-            }
-#undef QK_LAST32
+        if (base == 0 && xc) {
+            auto kern = k_encode_u32_bsgs_x80<16, 1>;
+            rc = run_pass(kern, 80, [&](uint32_t nb, uint64_t *partials) {
+                launch(kern, nb, s, ids, (uint64_t)n, head, Tp, partials, (const uint32_t *)nullptr, xc);
+            });
+        } else if (base == 0) {
+            auto kern = k_encode_u32_bsgs<8, 10, 16, 1>;
+            rc = run_pass(kern, 80, [&](uint32_t nb, uint64_t *partials) {
+                launch(kern, nb, s, ids, (uint64_t)n, head, Tp, partials);
+            });
+        } else if (Tp <= 40) {   // the last pass (npass >= 1): NA = ceil(Tp / 8) giant rows; <= 8 powers: one (x^base)
+            rc = with_int((Tp + 7) / 8, ints<1, 2, 3, 4, 5>{}, QK_E_THRESHOLD, [&](auto na) {
+                return with_int(xcm & 1, ints<0, 1>{}, QK_E_THRESHOLD, [&](auto x) { return off(na, x); });
+            });
         } else {
-            switch (xcm) {
-            case 1: rc = run_pass<1>(ctx, QK_OFF32(6, 1), 48, ids, n, head, Tp, base, out + base,
-                                        meta, acc, s, xc, nullptr); break;
-            case 2: rc = run_pass<1>(ctx, QK_OFF32(6, 2), 48, ids, n, head, Tp, base, out + base,
-                                        meta, acc, s, nullptr, xc); break;
-            case 3: rc = run_pass<1>(ctx, QK_OFF32(6, 3), 48, ids, n, head, Tp, base, out + base,
-                                        meta, acc, s, xc, xc); break;
-            default: rc = run_pass<1>(ctx, QK_OFF32(6, 0), 48, ids, n, head, Tp, base, out + base,
-                                         meta, acc, s); break;
-            }
-#undef QK_OFF32
+            rc = with_int(xcm, ints<0, 1, 2, 3>{}, QK_E_THRESHOLD,
+                          [&](auto x) { return off(std::integral_constant<int, 6>{}, x); });
         }
         if (rc) return rc;
         base += Tp;
-    }
-    return QK_OK;
-}
-
-// The x^base cache holds 4 B per id for the whole array: above XC_CHUNK32 ids
-// the passes run chunk by chunk (each chunk all its passes, the later chunks
-// accumulating into out), so the scratch stays <= 1 GiB.
-constexpr size_t XC_CHUNK32 = (size_t)1 << 28;
-static int enc32_passes(qk_ctx *ctx, const uint32_t *ids, size_t n, uint32_t head, uint32_t T, uint64_t *out,
-                        int acc, hipStream_t s) {
-    if (n <= XC_CHUNK32) return enc32_passes_chunk(ctx, ids, n, head, T, out, acc, s);
-    for (size_t c0 = 0; c0 < n; c0 += XC_CHUNK32) {
-        const uint32_t *p = ids + c0;
-        const uint32_t hd = (uint32_t)(((16 - ((uintptr_t)p & 15)) & 15) / 4);
-        if (int rc = enc32_passes_chunk(ctx, p, std::min(XC_CHUNK32, n - c0), hd, T, out, c0 ? 1 : acc, s)) return rc;
     }
     return QK_OK;
 }
@@ -875,202 +825,134 @@ static int enc32_passes(qk_ctx *ctx, const uint32_t *ids, size_t n, uint32_t hea
 // x^(base + 8a), every row a MAC row; NA = ceil(Tp / 8)).  Each pass reads the
 // 8-byte ids once more: at ~25 ms of integer issue per pass over 1e9 ids, the
 // extra 1 ms of HBM reads is noise.
-template <int NA, int XC = 0>
-static int run_pass64(qk_ctx *ctx, const uint64_t *ids, size_t n, uint32_t head, uint32_t Tp, uint32_t base,
-                      uint64_t *out, uint64_t *meta, int acc, hipStream_t s, uint64_t *xc = nullptr) {
-    auto kern = k_encode_u64_bsgs_off<NA, XC, 1>;
-    const uint32_t nb = grid_for(ctx, kern, (n + bsgs64::BLOCK - 1) / bsgs64::BLOCK, 1);
-    if (int rc = ensure_scratch(ctx, (size_t)nb * 2 * 8 * NA * sizeof(uint64_t), s)) return rc;
-    uint64_t *partials = (uint64_t *)ctx->d_scratch;
-    if (int rc = scratch_acquire(ctx, s)) return rc;
-    hipEvent_t e0 = prof_begin(ctx, s);
-    hipLaunchKernelGGL(kern, dim3(nb), dim3(BLOCK), 0, s, ids, (uint64_t)n, head, Tp, base, partials,
-                       (const uint64_t *)xc, xc);
-    prof_end(ctx, s, e0);
-    QK_HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_finalize_u64_pass, dim3(Tp), dim3(BLOCK), 0, s, partials, nb, Tp, ids, (uint64_t)n, out,
-                       meta, acc);
-    QK_HIP_TRY(hipGetLastError());
-    return scratch_release(ctx, s);
-}
-
-static int enc64_passes_chunk(qk_ctx *ctx, const uint64_t *ids, size_t n, uint32_t head, uint32_t T, uint64_t *out,
-                              int acc, hipStream_t s) {
-    uint64_t *meta = out + 2 * T;
+static int enc_passes_chunk(qk_ctx *ctx, const uint64_t *ids, size_t n, uint32_t head, uint32_t T, uint64_t *out,
+                            int acc, hipStream_t s) {
     // x^(next base) goes from pass to pass through a per-id cache (8 B read +
     // 8 B written per id and pass; pass 0 writes x^80) instead of each offset
-    // pass raising x^8 to base/8 (as enc32_passes).  The cache follows the
+    // pass raising x^8 to base/8 (as the u32 passes).  The cache follows the
     // partials in the scratch, sized once.
     const uint32_t npass = (T - 80 + 79) / 80;
+    const uint64_t tiles = (n + bsgs64::BLOCK - 1) / bsgs64::BLOCK;
     uint64_t *xc = nullptr;
     if (npass >= 1) {
-        const uint64_t tiles = (n + bsgs64::BLOCK - 1) / bsgs64::BLOCK;
         const uint32_t nbmax = grid_cap(ctx, tiles, 1);
         const size_t poff = ((size_t)nbmax * 2 * 80 * sizeof(uint64_t) + 255) & ~(size_t)255;
         if (ensure_scratch(ctx, poff + (size_t)n * 8, s) == QK_OK) xc = (uint64_t *)((char *)ctx->d_scratch + poff);
     }
-    {   // pass 0: powers 1..80 (+ x^80 per id for pass 1 when the cache is on)
-        auto kern = k_encode_u64_bsgs<10, 14, 1>;
-        auto kx80 = k_encode_u64_bsgs_x80<1>;
-        const uint32_t nb = grid_for(ctx, kern, (n + bsgs64::BLOCK - 1) / bsgs64::BLOCK, 1);
-        if (int rc = ensure_scratch(ctx, (size_t)nb * 2 * 80 * sizeof(uint64_t), s)) return rc;
-        uint64_t *partials = (uint64_t *)ctx->d_scratch;
-        if (int rc = scratch_acquire(ctx, s)) return rc;
-        hipEvent_t e0 = prof_begin(ctx, s);
-        if (xc)
-            hipLaunchKernelGGL(kx80, dim3(nb), dim3(BLOCK), 0, s, ids, (uint64_t)n, head, 80u, partials, xc);
-        else
-            hipLaunchKernelGGL(kern, dim3(nb), dim3(BLOCK), 0, s, ids, (uint64_t)n, head, 80u, partials);
-        prof_end(ctx, s, e0);
-        QK_HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_finalize_u64_pass, dim3(80), dim3(BLOCK), 0, s, partials, nb, 80u, ids, (uint64_t)n,
-                           out, meta, acc);
-        QK_HIP_TRY(hipGetLastError());
-        if (int rc = scratch_release(ctx, s)) return rc;
-    }
+    // one pass of Tp powers from base + 1: main(nb, partials) launches its
+    // kernel on the grid of kern (8 NA x 2 partial rows per workgroup); count
+    // and last id go with pass 0
+    auto run_pass = [&](auto kern, uint32_t NA, uint32_t Tp, uint32_t base, auto main) {
+        const uint32_t nb = grid_for(ctx, kern, tiles, 1);
+        return launch_encode(ctx, nb, (size_t)nb * 2 * 8 * NA * sizeof(uint64_t), s, main,
+                             finalize_to(Tp, ids, n, out + 2 * base, base == 0 ? out + 2 * T : nullptr, acc, s));
+    };
+    // pass 0: powers 1..80 (+ x^80 per id for pass 1 when the cache is on)
+    if (int rc = run_pass(k_encode_u64_bsgs<10, 14, 1>, 10, 80, 0, [&](uint32_t nb, uint64_t *partials) {
+            if (xc) launch(k_encode_u64_bsgs_x80<1>, nb, s, ids, (uint64_t)n, head, 80u, partials, xc);
+            else launch(k_encode_u64_bsgs<10, 14, 1>, nb, s, ids, (uint64_t)n, head, 80u, partials);
+        }))
+        return rc;
     uint32_t pass = 1;
     for (uint32_t base = 80; base < T; ++pass) {
         const uint32_t Tp = std::min<uint32_t>(80, T - base);
-        uint64_t *o = out + 2 * base;
+        // an offset pass of NA giant rows; XC: the cache read (bit 0) and written (bit 1)
+        auto off = [&](auto na, auto x) {
+            constexpr int NA = decltype(na)::value, XC = decltype(x)::value;
+            auto kern = k_encode_u64_bsgs_off<NA, XC, 1>;
+            uint64_t *c = XC ? xc : nullptr;
+            return run_pass(kern, NA, Tp, base, [&](uint32_t nb, uint64_t *partials) {
+                launch(kern, nb, s, ids, (uint64_t)n, head, Tp, base, partials, (const uint64_t *)c, c);
+            });
+        };
         // pass 0 wrote the cache; the middle passes read and write it (all
         // full 80-power passes), the last one reads it
         const int xcm = !xc ? 0 : 1 | (pass < npass ? 2 : 0);
         int rc;
-#define QK_PASS64(NA_)                                                                              \
-    (xcm & 1 ? run_pass64<NA_, 1>(ctx, ids, n, head, Tp, base, o, nullptr, acc, s, xc)           \
-             : run_pass64<NA_, 0>(ctx, ids, n, head, Tp, base, o, nullptr, acc, s))
-        if (xcm & 2) {   // a middle pass: Tp = 80
-            rc = run_pass64<10, 3>(ctx, ids, n, head, Tp, base, o, nullptr, acc, s, xc);
-        } else {
-            switch ((Tp + 7) / 8) {   // a last pass of <= 8 powers: one giant row (x^base)
-            case 1: rc = QK_PASS64(1); break;
-            case 2: rc = QK_PASS64(2); break;
-            case 3: rc = QK_PASS64(3); break;
-            case 4: rc = QK_PASS64(4); break;
-            case 5: rc = QK_PASS64(5); break;
-            case 6: rc = QK_PASS64(6); break;
-            case 7: rc = QK_PASS64(7); break;
-            case 8: rc = QK_PASS64(8); break;
-            case 9: rc = QK_PASS64(9); break;
-            default: rc = QK_PASS64(10); break;
-            }
-        }
-#undef QK_PASS64
+        if (xcm & 2)   // a middle pass: Tp = 80
+            rc = off(std::integral_constant<int, 10>{}, std::integral_constant<int, 3>{});
+        else   // a last pass of <= 8 powers: one giant row (x^base)
+            rc = with_int((Tp + 7) / 8, ints<1, 2, 3, 4, 5, 6, 7, 8, 9, 10>{}, QK_E_THRESHOLD, [&](auto na) {
+                return with_int(xcm & 1, ints<0, 1>{}, QK_E_THRESHOLD, [&](auto x) { return off(na, x); });
+            });
         if (rc) return rc;
         base += Tp;
     }
     return QK_OK;
 }
 
-// as enc32_passes: 8 B of cache per id, chunks of XC_CHUNK64 ids (1 GiB)
-constexpr size_t XC_CHUNK64 = (size_t)1 << 27;
-static int enc64_passes(qk_ctx *ctx, const uint64_t *ids, size_t n, uint32_t head, uint32_t T, uint64_t *out,
-                        int acc, hipStream_t s) {
-    if (n <= XC_CHUNK64) return enc64_passes_chunk(ctx, ids, n, head, T, out, acc, s);
-    for (size_t c0 = 0; c0 < n; c0 += XC_CHUNK64) {
-        const uint64_t *p = ids + c0;
-        const uint32_t hd = (uint32_t)(((16 - ((uintptr_t)p & 15)) & 15) / 8);
-        if (int rc = enc64_passes_chunk(ctx, p, std::min(XC_CHUNK64, n - c0), hd, T, out, c0 ? 1 : acc, s)) return rc;
+// The x^base cache holds one word of the id's width per id for the whole
+// array: above 1 GiB of it (2^28 u32 ids, 2^27 u64 ids) the passes run chunk
+// by chunk (each chunk all its passes, the later chunks accumulating into
+// out), so the scratch stays <= 1 GiB.
+template <typename IdT>
+static int enc_passes(qk_ctx *ctx, const IdT *ids, size_t n, uint32_t head, uint32_t T, uint64_t *out, int acc,
+                      hipStream_t s) {
+    constexpr size_t CHUNK = ((size_t)1 << 30) / sizeof(IdT);
+    if (n <= CHUNK) return enc_passes_chunk(ctx, ids, n, head, T, out, acc, s);
+    for (size_t c0 = 0; c0 < n; c0 += CHUNK) {
+        const IdT *p = ids + c0;
+        const uint32_t hd = (uint32_t)(((16 - ((uintptr_t)p & 15)) & 15) / sizeof(IdT));
+        if (int rc = enc_passes_chunk(ctx, p, std::min(CHUNK, n - c0), hd, T, out, c0 ? 1 : acc, s)) return rc;
     }
     return QK_OK;
 }
 
-// Choose (G, K): the smallest G whose K = ceil(T/G) fits the register
-// budget, then the smallest instantiated K >= ceil(T/G).
-static const int K32_G1[] = {1, 2, 4, 8, 12, 16, 20, 24, 28, 32};
-static const int K32_GN[] = {20, 24, 28, 32};
-static const int K64_G1[] = {1, 2, 4, 8, 12, 16, 20, 24, 32, 40};
-static const int K64_GN[] = {12, 16, 20, 24, 32, 40};
+// Power chains, (G, K): the smallest G whose K = ceil(T/G) fits the register
+// budget KMAX, then the smallest instantiated K >= ceil(T/G) — of KG1 at
+// G = 1, of KGN above; gk(G, K) runs the encode.
+using K32_G1 = ints<1, 2, 4, 8, 12, 16, 20, 24, 28, 32>;
+using K32_GN = ints<20, 24, 28, 32>;
+using K64_G1 = ints<1, 2, 4, 8, 12, 16, 20, 24, 32, 40>;
+using K64_GN = ints<12, 16, 20, 24, 32, 40>;
 
-template <int G, int K>
-static int enc32_gk(qk_ctx *ctx, const uint32_t *ids, size_t n, uint32_t head, uint32_t T, uint64_t *out,
-                    int acc, hipStream_t s) {
-    if constexpr (G == 1)
-        return run_encode<uint32_t>(ctx, k_encode_u32_g1<K>, k_finalize_u32, K, 1, ids, n, head, T,
-                                    (n + 3) / 4, BLOCK, out, acc, s);
-    else
-        return run_encode<uint32_t>(ctx, k_encode_u32_gn<G, K>, k_finalize_u32, G * K, 1, ids, n, head, T,
-                                    n, BLOCK / G, out, acc, s);
-}
-
-template <int G>
-static int enc32_g(qk_ctx *ctx, int K, const uint32_t *ids, size_t n, uint32_t head, uint32_t T, uint64_t *out,
-                   int acc, hipStream_t s) {
-    if constexpr (G == 1) {
-        switch (K) {
-        case 1: return enc32_gk<1, 1>(ctx, ids, n, head, T, out, acc, s);
-        case 2: return enc32_gk<1, 2>(ctx, ids, n, head, T, out, acc, s);
-        case 4: return enc32_gk<1, 4>(ctx, ids, n, head, T, out, acc, s);
-        case 8: return enc32_gk<1, 8>(ctx, ids, n, head, T, out, acc, s);
-        case 12: return enc32_gk<1, 12>(ctx, ids, n, head, T, out, acc, s);
-        case 16: return enc32_gk<1, 16>(ctx, ids, n, head, T, out, acc, s);
-        case 20: return enc32_gk<1, 20>(ctx, ids, n, head, T, out, acc, s);
-        case 24: return enc32_gk<1, 24>(ctx, ids, n, head, T, out, acc, s);
-        case 28: return enc32_gk<1, 28>(ctx, ids, n, head, T, out, acc, s);
-        case 32: return enc32_gk<1, 32>(ctx, ids, n, head, T, out, acc, s);
-        }
-    } else {
-        switch (K) {
-        case 20: return enc32_gk<G, 20>(ctx, ids, n, head, T, out, acc, s);
-        case 24: return enc32_gk<G, 24>(ctx, ids, n, head, T, out, acc, s);
-        case 28: return enc32_gk<G, 28>(ctx, ids, n, head, T, out, acc, s);
-        case 32: return enc32_gk<G, 32>(ctx, ids, n, head, T, out, acc, s);
-        }
+template <int... Ks>
+static int pick_k(uint32_t kneed, ints<Ks...>) {
+    int K = 0;
+    for (int k : {Ks...}) {
+        K = k;
+        if ((uint32_t)k >= kneed) break;
     }
-    return QK_E_THRESHOLD;
+    return K;
 }
 
-template <int G, int K>
-static int enc64_gk(qk_ctx *ctx, const uint64_t *ids, size_t n, uint32_t head, uint32_t T, uint64_t *out,
-                    int acc, hipStream_t s) {
-    if constexpr (G == 1)
-        return run_encode<uint64_t>(ctx, k_encode_u64_g1<K>, k_finalize_u64, K, 2, ids, n, head, T,
-                                    (n + 1) / 2, BLOCK, out, acc, s);
-    else
-        return run_encode<uint64_t>(ctx, k_encode_u64_gn<G, K>, k_finalize_u64, G * K, 2, ids, n, head, T,
-                                    n, BLOCK / G, out, acc, s);
-}
-
-template <int G>
-static int enc64_g(qk_ctx *ctx, int K, const uint64_t *ids, size_t n, uint32_t head, uint32_t T, uint64_t *out,
-                   int acc, hipStream_t s) {
-    if constexpr (G == 1) {
-        switch (K) {
-        case 1: return enc64_gk<1, 1>(ctx, ids, n, head, T, out, acc, s);
-        case 2: return enc64_gk<1, 2>(ctx, ids, n, head, T, out, acc, s);
-        case 4: return enc64_gk<1, 4>(ctx, ids, n, head, T, out, acc, s);
-        case 8: return enc64_gk<1, 8>(ctx, ids, n, head, T, out, acc, s);
-        case 12: return enc64_gk<1, 12>(ctx, ids, n, head, T, out, acc, s);
-        case 16: return enc64_gk<1, 16>(ctx, ids, n, head, T, out, acc, s);
-        case 20: return enc64_gk<1, 20>(ctx, ids, n, head, T, out, acc, s);
-        case 24: return enc64_gk<1, 24>(ctx, ids, n, head, T, out, acc, s);
-        case 32: return enc64_gk<1, 32>(ctx, ids, n, head, T, out, acc, s);
-        case 40: return enc64_gk<1, 40>(ctx, ids, n, head, T, out, acc, s);
-        }
-    } else {
-        switch (K) {
-        case 12: return enc64_gk<G, 12>(ctx, ids, n, head, T, out, acc, s);
-        case 16: return enc64_gk<G, 16>(ctx, ids, n, head, T, out, acc, s);
-        case 20: return enc64_gk<G, 20>(ctx, ids, n, head, T, out, acc, s);
-        case 24: return enc64_gk<G, 24>(ctx, ids, n, head, T, out, acc, s);
-        case 32: return enc64_gk<G, 32>(ctx, ids, n, head, T, out, acc, s);
-        case 40: return enc64_gk<G, 40>(ctx, ids, n, head, T, out, acc, s);
-        }
-    }
-    return QK_E_THRESHOLD;
-}
-
-static void choose_gk(uint32_t T, int kmax, const int *kg1, int nkg1, const int *kgn, int nkgn, int &G, int &K) {
-    G = 1;
-    while ((T + G - 1) / G > (uint32_t)kmax) G *= 2;
+template <int KMAX, class KG1, class KGN, int... Gs, class F>
+static int enc_chain(uint32_t T, ints<Gs...> gs, F &&gk) {
+    int G = 1;
+    while ((T + G - 1) / G > (uint32_t)KMAX) G *= 2;
     const uint32_t kneed = (T + G - 1) / G;
-    const int *ks = G == 1 ? kg1 : kgn;
-    const int nk = G == 1 ? nkg1 : nkgn;
-    K = ks[nk - 1];
-    for (int i = 0; i < nk; ++i)
-        if ((uint32_t)ks[i] >= kneed) { K = ks[i]; break; }
+    return with_int(G, gs, QK_E_THRESHOLD, [&](auto g) {
+        using KS = std::conditional_t<decltype(g)::value == 1, KG1, KGN>;
+        return with_int(pick_k(kneed, KS{}), KS{}, QK_E_THRESHOLD, [&](auto k) { return gk(g, k); });
+    });
 }
 
+// The single-pass u32 BSGS shapes with scalar-counted wraps, by threshold:
+//   X(t_lo, t_hi, NB, NA, SG)
+// 5..28: four babies and ceil(T / 4) giant rows (every group 4 wide); above,
+// the round-3 shapes: the (NB, NA) with the fewest issue cycles for the
+// powers actually needed — modmuls NB - 1 + NA - 2 at ~17 cycles, MACs
+// NB (NA - 1) and row-0 adds NB at ~4.2, measured ((6,4) /
+// (8,4) computed 24 / 32 powers at 17..28): 29..30 (6,5), 33..36 (6,6),
+// 41..42 (6,7), 65..72 (8,9).  tools/issue_model.py u32_shape prices the same
+// rows (tests/test_issue_model.py holds the two together).
+#define QK_U32_SHAPES(X)           \
+    X(5, 8, 4, 2, 1)               \
+    X(9, 12, 4, 3, 3)              \
+    X(13, 16, 4, 4, 4)             \
+    X(17, 20, 4, 5, 5)             \
+    X(21, 24, 4, 6, 6)             \
+    X(25, 28, 4, 7, 7)             \
+    X(29, 30, 6, 5, 5)             \
+    X(31, 32, 8, 4, QK_BSGS_SG_T32) \
+    X(33, 36, 6, 6, 6)             \
+    X(37, 40, 8, 5, 10)            \
+    X(41, 42, 6, 7, 7)             \
+    X(43, 48, 8, 6, 12)            \
+    X(49, 56, 8, 7, 14)            \
+    X(57, 64, 8, 8, 16)            \
+    X(65, 72, 8, 9, 14)            \
+    X(73, 80, 8, 10, 16)
 
 static int enc32(qk_ctx *ctx, const uint32_t *ids, size_t n, uint32_t T, uint64_t *out, int acc, hipStream_t s) {
     if (T == 0 || T > QK_MAX_THRESHOLD) return QK_E_THRESHOLD;
@@ -1078,8 +960,8 @@ static int enc32(qk_ctx *ctx, const uint32_t *ids, size_t n, uint32_t T, uint64_
     if (a & 3) return QK_E_INVAL;
     const uint32_t head = (uint32_t)(((16 - (a & 15)) & 15) / 4);
     if (n >= (1ull << 40)) return QK_E_INVAL; // 4 TB of ids: beyond any HBM; keeps per-lane trip counts 32-bit
-    // baby-step / giant-step for 9 <= T <= 32 (fewer modmuls per id); the
-    // power chain otherwise
+    // baby-step / giant-step for the thresholds of QK_U32_SHAPES (fewer
+    // modmuls per id) and, in passes, above them; the power chain otherwise
     // Scalar-counted BSGS groups (bsgs.h) keep per-wave 32-bit wrap totals: a
     // wave sees at most 64 * (4 * trips + 2) wraps per accumulator, so trips
     // must stay < 2^24 - 1 — true for any n < 2^40 at >= 1 workgroup per CU;
@@ -1091,62 +973,40 @@ static int enc32(qk_ctx *ctx, const uint32_t *ids, size_t n, uint32_t T, uint64_
     // alone could take every chunk: < 2^32 wraps per accumulator); longer
     // streams keep the static split.
     const bool dyn = ctx->knobs.enc_dyn != 0 && n < (1ull << 32);
-#define QK_BSGS_STATIC(NB_, NA_, G_)                                                                          \
-    run_encode<uint32_t>(ctx, k_encode_u32_bsgs<NB_, NA_, G_, 1>, k_finalize_u32, NB_ * NA_, 1, ids, n, head, T, \
-                         (n + 3) / 4, BLOCK, out, acc, s, NB_ * NA_ > 48 ? 1 : 0)
-#define QK_BSGS(NB_, NA_, G_)                                                                                 \
-    (dyn ? run_encode_dyn(ctx, k_encode_u32_bsgs_dyn<NB_, NA_, G_, 1>, k_finalize_u32, NB_ * NA_, ids, n, head, T, \
-                          out, acc, s)                                                                        \
+#define QK_BSGS_STATIC(NB_, NA_, G_)                                                                      \
+    run_encode(ctx, k_encode_u32_bsgs<NB_, NA_, G_, 1>, NB_ * NA_, ids, n, head, T, (n + 3) / 4, BLOCK, out, acc, s, \
+               NB_ * NA_ > 48 ? 1 : 0)
+#define QK_BSGS(NB_, NA_, G_)                                                                             \
+    (dyn ? run_encode_dyn(ctx, k_encode_u32_bsgs_dyn<NB_, NA_, G_, 1>, NB_ * NA_, ids, n, head, T, out, acc, s) \
          : QK_BSGS_STATIC(NB_, NA_, G_))
-    if (T >= 5 && T <= 8 && sc_ok) return QK_BSGS(4, 2, 1);
-    if (T >= 9 && T <= 12) return sc_ok ? QK_BSGS(4, 3, 3) : QK_BSGS_STATIC(4, 3, 0);
-    if (T >= 13 && T <= 16) return sc_ok ? QK_BSGS(4, 4, 4) : QK_BSGS_STATIC(4, 4, 0);
-    // Round-3 shapes: the (NB, NA) with the fewest issue cycles for the
-    // powers actually needed — modmuls NB - 1 + NA - 2 at ~17 cycles, MACs
-    // NB (NA - 1) and row-0 adds NB at ~4.2, measured: 17..28
-    // four babies and ceil(T / 4) giant rows (every group 4 wide,
-    // scalar-counted; (6,4) / (8,4) computed 24 / 32 powers), 29..30 (6,5),
-    // 33..36 (6,6), 41..42 (6,7), 65..72 (8,9)
+#define QK_BSGS_ROW(LO_, HI_, NB_, NA_, G_) \
+    if (T >= LO_ && T <= HI_) return QK_BSGS(NB_, NA_, G_);
     if (sc_ok) {
-        if (T >= 17 && T <= 20) return QK_BSGS(4, 5, 5);
-        if (T >= 21 && T <= 24) return QK_BSGS(4, 6, 6);
-        if (T >= 25 && T <= 28) return QK_BSGS(4, 7, 7);
-        if (T >= 29 && T <= 30) return QK_BSGS(6, 5, 5);
         if (T >= 31 && T <= 32 && ctx->knobs.u32_basis != 0)   // the nine-power basis (basis32.h)
-            return dyn ? run_encode_dyn(ctx, k_encode_u32_basis_dyn<1>, k_finalize_u32, 32, ids, n, head, T, out, acc,
-                                        s)
-                       : run_encode<uint32_t>(ctx, k_encode_u32_basis<1>, k_finalize_u32, 32, 1, ids, n, head, T,
-                                              (n + 3) / 4, BLOCK, out, acc, s, 0);
-        if (T >= 31 && T <= 32) return QK_BSGS(8, 4, QK_BSGS_SG_T32);
-        if (T >= 33 && T <= 36) return QK_BSGS(6, 6, 6);
-        if (T >= 37 && T <= 40) return QK_BSGS(8, 5, 10);
-        if (T >= 41 && T <= 42) return QK_BSGS(6, 7, 7);
-        if (T >= 43 && T <= 48) return QK_BSGS(8, 6, 12);
-        if (T >= 49 && T <= 56) return QK_BSGS(8, 7, 14);
-        if (T >= 57 && T <= 64) return QK_BSGS(8, 8, 16);
-        if (T >= 65 && T <= 72) return QK_BSGS(8, 9, 14);
-        if (T >= 73 && T <= 80) return QK_BSGS(8, 10, 16);
-        if (T > 80) return enc32_passes(ctx, ids, n, head, T, out, acc, s);
+            return dyn ? run_encode_dyn(ctx, k_encode_u32_basis_dyn<1>, 32, ids, n, head, T, out, acc, s)
+                       : run_encode(ctx, k_encode_u32_basis<1>, 32, ids, n, head, T, (n + 3) / 4, BLOCK, out, acc, s,
+                                    0);
+        QK_U32_SHAPES(QK_BSGS_ROW)
+        if (T > 80) return enc_passes(ctx, ids, n, head, T, out, acc, s);
     } else {
         // the all-VALU forms that fit the registers; t 33..80 would spill, so
         // a grid too small for scalar counts takes the power chain there
         // (static only: !sc_ok needs n >= 2^34, beyond the dynamic form)
+        if (T >= 9 && T <= 12) return QK_BSGS_STATIC(4, 3, 0);
+        if (T >= 13 && T <= 16) return QK_BSGS_STATIC(4, 4, 0);
         if (T >= 17 && T <= 24) return QK_BSGS_STATIC(6, 4, 0);
         if (T >= 25 && T <= 32) return QK_BSGS_STATIC(8, 4, 0);
     }
+#undef QK_BSGS_ROW
 #undef QK_BSGS
 #undef QK_BSGS_STATIC
-    int G, K;
-    choose_gk(T, 32, K32_G1, 10, K32_GN, 4, G, K);
-    switch (G) {
-    case 1: return enc32_g<1>(ctx, K, ids, n, head, T, out, acc, s);
-    case 2: return enc32_g<2>(ctx, K, ids, n, head, T, out, acc, s);
-    case 4: return enc32_g<4>(ctx, K, ids, n, head, T, out, acc, s);
-    case 8: return enc32_g<8>(ctx, K, ids, n, head, T, out, acc, s);
-    case 16: return enc32_g<16>(ctx, K, ids, n, head, T, out, acc, s);
-    case 32: return enc32_g<32>(ctx, K, ids, n, head, T, out, acc, s);
-    }
-    return QK_E_THRESHOLD;
+    return enc_chain<32, K32_G1, K32_GN>(T, ints<1, 2, 4, 8, 16, 32>{}, [&](auto g, auto k) {
+        constexpr int G = decltype(g)::value, K = decltype(k)::value;
+        if constexpr (G == 1)   // each lane streams ids with 16-byte loads
+            return run_encode(ctx, k_encode_u32_g1<K>, K, ids, n, head, T, (n + 3) / 4, BLOCK, out, acc, s);
+        else
+            return run_encode(ctx, k_encode_u32_gn<G, K>, G * K, ids, n, head, T, n, BLOCK / G, out, acc, s);
+    });
 }
 
 static int enc64(qk_ctx *ctx, const uint64_t *ids, size_t n, uint32_t T, uint64_t *out, int acc, hipStream_t s) {
@@ -1163,55 +1023,35 @@ static int enc64(qk_ctx *ctx, const uint64_t *ids, size_t n, uint32_t T, uint64_
     const uint64_t min_grid64 = ctx->grid_override ? ctx->grid_override : (uint64_t)ctx->num_cus;
     const bool bsgs_ok = n / min_grid64 < (1ull << 30);
     if (T >= 14 && T <= 80 && bsgs_ok) {
-#define QK_BSGS64(NA_, SG_)                                                                           \
-    run_encode<uint64_t>(ctx, k_encode_u64_bsgs<NA_, SG_, 1>, k_finalize_u64, 8 * NA_, 2, ids, n, head, T,   \
-                         (n + bsgs64::BLOCK - 1) / bsgs64::BLOCK, 1, out, acc, s)
-#define QK_BSGS64_4(NA_)                                                                              \
-    run_encode<uint64_t>(ctx, k_encode_u64_bsgs4<NA_, 1>, k_finalize_u64, 4 * NA_, 2, ids, n, head, T,      \
-                         (n + bsgs64::BLOCK - 1) / bsgs64::BLOCK, 1, out, acc, s)
+        const uint64_t tiles = (n + bsgs64::BLOCK - 1) / bsgs64::BLOCK;
         // four babies per id and ceil(T/4) giant rows where 8 babies would
         // compute 4+ powers more: t = 14..20, 25..28, 33..36 (+8..17 %,
         // profiles/r03/shapes/sweep64_four_babies_ab.jsonl; at t = 21..24,
         // 29..32 even, at 37..40 7 % slower: not used)
-        if (T <= 36) switch ((T + 3) / 4) {
-            case 4: return QK_BSGS64_4(4);
-            case 5: return QK_BSGS64_4(5);
-            case 7: return QK_BSGS64_4(7);
-            case 9: return QK_BSGS64_4(9);
-            default: break;
-            }
-#undef QK_BSGS64_4
-        switch ((T + 7) / 8) {   // NA <= 9: a wave's <= 16 MACs all scalar-counted
-        case 2: return QK_BSGS64(2, 16);
-        case 3: return QK_BSGS64(3, 16);
-        case 4: return QK_BSGS64(4, 16);
-        case 5: return QK_BSGS64(5, 16);
-        case 6: return QK_BSGS64(6, 16);
-        case 7: return QK_BSGS64(7, 16);
-        case 8: return QK_BSGS64(8, 16);
-        case 9: return QK_BSGS64(9, 16);
-        // NA = 10: 14 of the 18 MACs scalar-counted with the paired-MAC form
-        // (22.65 vs 23.19 ms at 16, twice, profiles/r04/prio/tune_u64_prio.json)
-        default: return QK_BSGS64(10, 14);
-        }
-#undef QK_BSGS64
+        const int rc4 = with_int(T <= 36 ? (T + 3) / 4 : 0, ints<4, 5, 7, 9>{}, 1, [&](auto na) {
+            constexpr int NA = decltype(na)::value;
+            return run_encode(ctx, k_encode_u64_bsgs4<NA, 1>, 4 * NA, ids, n, head, T, tiles, 1, out, acc, s);
+        });
+        if (rc4 <= 0) return rc4;   // 1: no four-baby form at this T (a status is <= 0)
+        return with_int((T + 7) / 8, ints<2, 3, 4, 5, 6, 7, 8, 9, 10>{}, QK_E_THRESHOLD, [&](auto na) {
+            // NA <= 9: a wave's <= 16 MACs all scalar-counted
+            // NA = 10: 14 of the 18 MACs scalar-counted with the paired-MAC form
+            // (22.65 vs 23.19 ms at 16, twice, profiles/r04/prio/tune_u64_prio.json)
+            constexpr int NA = decltype(na)::value, SG = NA == 10 ? 14 : 16;
+            return run_encode(ctx, k_encode_u64_bsgs<NA, SG, 1>, 8 * NA, ids, n, head, T, tiles, 1, out, acc, s);
+        });
     }
-    if (T > 80 && bsgs_ok) return enc64_passes(ctx, ids, n, head, T, out, acc, s);
-    int G, K;
+    if (T > 80 && bsgs_ok) return enc_passes(ctx, ids, n, head, T, out, acc, s);
     // K <= 40 accumulators per lane (120 VGPRs, 3 waves/SIMD) beat K <= 20 at
     // 5 waves by needing fewer lanes per id (t = 80: 2 x (39 + 1) steps vs
     // 4 x (19 + 3)).
-    choose_gk(T, 40, K64_G1, 10, K64_GN, 6, G, K);
-    switch (G) {
-    case 1: return enc64_g<1>(ctx, K, ids, n, head, T, out, acc, s);
-    case 2: return enc64_g<2>(ctx, K, ids, n, head, T, out, acc, s);
-    case 4: return enc64_g<4>(ctx, K, ids, n, head, T, out, acc, s);
-    case 8: return enc64_g<8>(ctx, K, ids, n, head, T, out, acc, s);
-    case 16: return enc64_g<16>(ctx, K, ids, n, head, T, out, acc, s);
-    case 32: return enc64_g<32>(ctx, K, ids, n, head, T, out, acc, s);
-    case 64: return enc64_g<64>(ctx, K, ids, n, head, T, out, acc, s);
-    }
-    return QK_E_THRESHOLD;
+    return enc_chain<40, K64_G1, K64_GN>(T, ints<1, 2, 4, 8, 16, 32, 64>{}, [&](auto g, auto k) {
+        constexpr int G = decltype(g)::value, K = decltype(k)::value;
+        if constexpr (G == 1)
+            return run_encode(ctx, k_encode_u64_g1<K>, K, ids, n, head, T, (n + 1) / 2, BLOCK, out, acc, s);
+        else
+            return run_encode(ctx, k_encode_u64_gn<G, K>, G * K, ids, n, head, T, n, BLOCK / G, out, acc, s);
+    });
 }
 
 int launch_encode_u32(qk_ctx *ctx, const uint32_t *d_ids, size_t n, uint32_t t, uint64_t *d_partial, hipStream_t s) {

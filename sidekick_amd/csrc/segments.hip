@@ -25,14 +25,8 @@ QK_WARM_KERNEL(segments)
 
 static_assert(sizeof(qk_u32) == 16, "qk_u32 header is 4 words (k_seg_small writes it)");
 
-constexpr int SG_BLOCK = 256;
-constexpr int SG_WAVES = SG_BLOCK / 64;
-
-__device__ __forceinline__ uint64_t sg_shfl_xor_u64(uint64_t v, int m) {
-    const uint32_t lo = __shfl_xor((int)(uint32_t)v, m, 64);
-    const uint32_t hi = __shfl_xor((int)(uint32_t)(v >> 32), m, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
+constexpr int SG_BLOCK = bsgs::BLOCK;
+constexpr int SG_WAVES = bsgs::WAVES;
 
 // lane j of a G-group: start = x^(j+1), step = x^G (canonical)
 template <int G>
@@ -77,7 +71,7 @@ __global__ __launch_bounds__(SG_BLOCK) void k_seg_encode(const uint32_t *__restr
     for (int k = 0; k < K; ++k) {
         uint64_t v = fold64_32(acc[k]);
 #pragma unroll
-        for (int off = 32; off >= G; off >>= 1) v += sg_shfl_xor_u64(v, off);
+        for (int off = 32; off >= G; off >>= 1) v += bsgs::shfl_xor_u64(v, off);
         if (lane < G) sm[wave * (G * K) + lane + k * G] = v;
     }
     __syncthreads();

@@ -54,10 +54,9 @@ def _run(bits, cases):
 
 
 def test_u32_every_bsgs_shape():
-    """Both ends of every u32 shape's range — (4,2) 5..8, (4,3) 9..12, (4,4)
-    13..16, (4,5..7) 17..28, (6,5) 29..30, (8,4) 31..32, (6,6) 33..36, (8,5)
-    37..40, (6,7) 41..42, (8,6..8) 43..64, (8,9) 65..72, (8,10) 73..80 — and
-    the chain below, ragged and misaligned."""
+    """Both ends of every u32 shape's range — the rows of QK_U32_SHAPES in
+    encode.hip, (4,2) at 5..8 to (8,10) at 73..80 — and the chain below,
+    ragged and misaligned."""
     ts = (1, 4, 5, 8, 9, 12, 13, 16, 17, 20, 21, 24, 25, 28, 29, 30, 31, 32, 33, 36, 37, 40, 41, 42, 43, 48, 49, 56,
           57, 64, 65, 72, 73, 80)
     res = _run(32, [(f"t{t}", 100_003 + t, t, t % 4) for t in ts])
@@ -169,6 +168,19 @@ def test_passes_saturated_grid():
     CU) must not overlap them."""
     res = _run_tiled(32, [("u32_t100", 100_003, 42, 100), ("u32_t200", 100_003, 42, 200)])
     res.update(_run_tiled(64, [("u64_t100", 50_021, 70, 100), ("u64_t200", 50_021, 70, 200)]))
+    assert all(res.values()), res
+
+
+def test_passes_chunked():
+    """Multi-pass encodes of more ids than one x^base cache of 1 GiB holds
+    (u32: > 2^28, u64: > 2^27) run chunk by chunk, the second chunk — short
+    here, 5.7e5 / 2.8e5 ids — accumulating into the first.  u32 t = 129:
+    passes of 80, 48 and 1 powers (a middle pass that reads and writes the
+    cache, a one-row last pass); u64 t = 161: 80, 80 and 1."""
+    res = _run_tiled(32, [("u32_t129", 1_000_003, 269, 129)])
+    assert 1_000_003 * 269 > 2**28
+    res.update(_run_tiled(64, [("u64_t161", 500_009, 269, 161)]))
+    assert 500_009 * 269 > 2**27
     assert all(res.values()), res
 
 

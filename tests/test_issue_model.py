@@ -28,6 +28,22 @@ def test_u32_shapes_cover_t(t):
     assert nb * na >= t and nb % 2 == 0
 
 
+def test_u32_shapes_are_the_dispatch_table():
+    """The model prices, at every t, the (NB, NA) the dispatcher launches: the
+    rows X(t_lo, t_hi, NB, NA, SG) of QK_U32_SHAPES, read out of encode.hip."""
+    import re
+    with open(os.path.join(ROOT, "sidekick_amd", "csrc", "encode.hip")) as f:
+        table = re.search(r"#define QK_U32_SHAPES\(X\)((?:[^\n]*\\\n)+[^\n]*\n)", f.read()).group(1)
+    rows = [tuple(int(v) for v in r) for r in re.findall(r"X\((\d+), (\d+), (\d+), (\d+), \w+\)", table)]
+    assert len(rows) == table.count("X(") == 16
+    assert rows[0][0] == 5 and rows[-1][1] == 80
+    assert all(a[1] + 1 == b[0] for a, b in zip(rows, rows[1:])) and all(lo <= hi for lo, hi, _, _ in rows)
+    assert (31, 32, 8, 4) in rows
+    want = {t: (nb, na) for lo, hi, nb, na in rows for t in range(lo, hi + 1)}
+    for t in range(1, 82):
+        assert issue_model.u32_shape(t) == want.get(t), t
+
+
 def test_u64_anchor_t80():
     a = issue_model.anchor(64, 80)
     assert a["shape"] == {"NBT": 8, "NA": 10}
