@@ -348,6 +348,10 @@ int qk_u32_to_coeffs_segments_device(qk_ctx *ctx, const uint8_t *diffs, size_t n
 /* Log entries per work item of the batched root test: a longer segment is cut
  * into slices of this many entries, one workgroup each. */
 #define QK_SEG_DECODE_ITEM 2048u
+/* Whole shorter segments are packed into one work item: a run ends after at most this many segments, */
+#define QK_SEG_DECODE_MAXSEG 256u
+/* and after at most QK_SEG_DECODE_COEF_WORDS / threshold (>= 1) of them: the words of their rows. */
+#define QK_SEG_DECODE_COEF_WORDS 8192u
 /* decode_with_log (media_client.rs:296-313) for nseg (diff, log segment)
  * pairs in one pass — the per-flow quACKs of sidekick_multi.rs:65-90 against
  * the sender's logs kept grouped by flow: d_log is a device array, segment g

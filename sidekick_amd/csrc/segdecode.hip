@@ -42,8 +42,8 @@ constexpr uint32_t SD_WORDS = SD_ITEM / 64;        // hit-mask words per work it
 static_assert(SD_ITEM % SD_BLOCK == 0 && SD_WORDS <= 64, "k_seg_hit_write: one lane per mask word");
 // LDS words for the coefficient rows of one packed work item: a run of short
 // segments ends after SD_COEF_WORDS / T segments (at most SD_MAXSEG)
-constexpr uint32_t SD_COEF_WORDS = 8192;
-constexpr uint32_t SD_MAXSEG = 256;
+constexpr uint32_t SD_COEF_WORDS = QK_SEG_DECODE_COEF_WORDS;
+constexpr uint32_t SD_MAXSEG = QK_SEG_DECODE_MAXSEG;
 
 struct SdItem {
     uint64_t lo;     // first log position
