@@ -162,7 +162,9 @@ int qk_ctx_set_grid(qk_ctx *ctx, uint32_t blocks);
  * baby-step/giant-step encode hands its ids out in chunks that waves claim,
  * one resident round; 0: the static form), "u32_basis" (1: the u32 t = 31..32
  * encode forms its 32 powers from a nine-power basis, 8 modular products per
- * id; 0: from the (8,4) baby-step/giant-step grid, 9), "flow_hist" (per-flow batches of at most this many
+ * id, with a table lookup per id for the ids whose lazy products wrap; 2: the same
+ * basis with a running minimum of the products instead of the lookup; 0: from
+ * the (8,4) baby-step/giant-step grid, 9), "flow_hist" (per-flow batches of at most this many
  * flows are grouped by slot histograms, 0: never), "flow_byslot" (0 the
  * rule, 1 / 2 force the by-slot / by-rank grouping key), "root_test" (0
  * automatic, 1 Horner, 2 root-set scan), "comm_fault" (tests: the k-th

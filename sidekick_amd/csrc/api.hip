@@ -708,7 +708,7 @@ int qk_ctx_set_knob(qk_ctx *ctx, const char *name, int64_t value) {
     static const K table[] = {
         {"grid_mult", &qk_knobs::grid_mult, 1, 8},
         {"enc_dyn", &qk_knobs::enc_dyn, 0, 1},
-        {"u32_basis", &qk_knobs::u32_basis, 0, 1},
+        {"u32_basis", &qk_knobs::u32_basis, 0, 2},
         {"flow_hist", &qk_knobs::flow_hist, 0, 1 << 20},
         {"flow_byslot", &qk_knobs::flow_byslot, 0, 2},
         {"root_test", &qk_knobs::root_test, 0, 2},

@@ -120,7 +120,10 @@ constexpr int mac_r(int i) { return vidx(TERM[MAC[i]].right); }
 // Lazy form: returns the minimum of the eight results; below WRAP_BELOW a
 // fold may have wrapped and the caller runs the exact form instead (field.h
 // mulfold32_min).  The kernel issues the same eight products as one asm
-// statement (bsgs.h BasisChain); this is its mirror on the CPU.
+// statement (bsgs.h basis_chain); this is its mirror on the CPU.  Which ids
+// the lazy form gets wrong is a fixed set of 61: the kernel looks them up
+// (basis_filter.h) instead of forming the minimum, which only the
+// u32_basis = 2 form still does.
 constexpr uint32_t WRAP_BELOW = 25u;
 QK_HD uint32_t chain_min(uint32_t id, uint32_t (&V)[NE]) {
     uint32_t mn = 0xFFFFFFFFu;

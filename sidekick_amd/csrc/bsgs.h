@@ -38,6 +38,7 @@
 #include <stdint.h>
 
 #include "basis32.h"
+#include "basis_filter.h"
 #include "field.h"
 
 namespace qk {
@@ -283,6 +284,7 @@ template <int NB_, int NA_, int SG_, int ROW0_ = 1, int FOLD_ = 1, bool PAIR_ = 
           int XC_ = 0, bool TREE_ = false, int PRIO_ = 0>
 struct Cfg {
     static constexpr bool BASIS = false;   // CfgBasis (below) sets it
+    static constexpr bool FILT = false;    // ... and this
     // PRIO  wave priority (s_setprio) over the accumulation: 4 (the product)
     //       row 0 at 1 and the MAC rows with their scalar wrap counts at 2,
     //       the powers at 0; (measurements) 1 the whole accumulation at 1,
@@ -302,9 +304,13 @@ struct Cfg {
 // The basis form: the plain (8, 4) configuration — its accumulators, every MAC
 // group scalar-counted, row 0 as multiply-adds, min-tracked folds — with the
 // flag set.  A derived type, so that no Cfg<...> instantiation is renamed.
-template <int PRIO_>
+// FILT 1: the ids whose lazy chain is wrong are found by the table of
+// basis_filter.h, once per trip of four ids; 0: by the minimum of each id's
+// eight products (knob u32_basis = 2, kept for comparison).
+template <int PRIO_, int FILT_ = 1>
 struct CfgBasis : Cfg<8, 4, 8, 1, 1, false, false, 0, false, PRIO_> {
     static constexpr bool BASIS = true;
+    static constexpr bool FILT = FILT_ != 0;
     static_assert(PRIO_ == 0 || PRIO_ == 4, "basis form: no priority change, or the product's two levels");
 };
 
@@ -467,10 +473,12 @@ QK_CHAINS(8)
 // ---- the nine-power basis (basis32.h) as one statement ----------------------
 // The same window and rules as LazyChain: Q in v[6:7], each result in the even
 // register of its own pair v[8:9] .. v[22:23] (V[1] .. V[8] in the order of
-// basis32::CHAIN), the odd halves clobbered, carry-outs to s[58:59], the
-// minimum of the eight results formed in the dead v9.  The text below is
-// basis32::CHAIN written out (checked underneath): 2 = 1+1, 3 = 2+1, 6 = 3+3,
-// 8 = 6+2, 12 = 6+6, 16 = 8+8, 13 = 12+1, 15 = 12+3.
+// basis32::CHAIN), the odd halves clobbered, carry-outs to s[58:59].  The text
+// below is basis32::CHAIN written out (checked underneath): 2 = 1+1, 3 = 2+1,
+// 6 = 3+3, 8 = 6+2, 12 = 6+6, 16 = 8+8, 13 = 12+1, 15 = 12+3.  The chain
+// carries no wrap check: the ids it gets wrong are known (basis_filter.h).
+// QK_BASIS_CHAIN_MIN is the form of CfgBasis<.., 0>: the minimum of the eight
+// results formed in the dead v9.
 #define QK_BASIS_CHAIN                                                                                 \
     QK_LP(8, 9, "%[id]", "%[id]")                                                                      \
     QK_LP(10, 11, "v8", "%[id]")                                                                       \
@@ -479,7 +487,9 @@ QK_CHAINS(8)
     QK_LP(16, 17, "v12", "v12")                                                                        \
     QK_LP(18, 19, "v14", "v14")                                                                        \
     QK_LP(20, 21, "v16", "%[id]")                                                                      \
-    QK_LP(22, 23, "v16", "v10")                                                                        \
+    QK_LP(22, 23, "v16", "v10")
+#define QK_BASIS_CHAIN_MIN                                                                             \
+    QK_BASIS_CHAIN                                                                                     \
     "v_min3_u32 v9, v8, v10, v12\n\t"                                                                  \
     "v_min3_u32 v9, v9, v14, v16\n\t"                                                                  \
     "v_min3_u32 v9, v9, v18, v20\n\t"                                                                  \
@@ -493,16 +503,48 @@ constexpr bool basis_chain_is(const uint8_t (&t)[3 * basis32::NP]) {
 }
 static_assert(basis_chain_is({2, 1, 1, 3, 2, 1, 6, 3, 3, 8, 6, 2, 12, 6, 6, 16, 8, 8, 13, 12, 1, 15, 12, 3}),
               "QK_BASIS_CHAIN is basis32::CHAIN written out");
-// V[0] = id, V[i + 1] = the chain's step i (lazy); returns their minimum
-__device__ __forceinline__ uint32_t basis_chain(uint32_t id, uint32_t (&V)[basis32::NE]) {
-    uint32_t mn;
+// V[0] = id, V[i + 1] = the chain's step i (lazy)
+__device__ __forceinline__ void basis_chain(uint32_t id, uint32_t (&V)[basis32::NE]) {
     V[0] = id;
     asm(QK_BASIS_CHAIN
+        : "=&{v8}"(V[1]), "=&{v10}"(V[2]), "=&{v12}"(V[3]), "=&{v14}"(V[4]), "=&{v16}"(V[5]), "=&{v18}"(V[6]),
+          "=&{v20}"(V[7]), "=&{v22}"(V[8])
+        : [id] "v"(id)
+        : "v6", "v7", "v9", "v11", "v13", "v15", "v17", "v19", "v21", "v23", "s58", "s59");
+}
+// ... and returns their minimum
+__device__ __forceinline__ uint32_t basis_chain_min(uint32_t id, uint32_t (&V)[basis32::NE]) {
+    uint32_t mn;
+    V[0] = id;
+    asm(QK_BASIS_CHAIN_MIN
         : "=&{v9}"(mn), "=&{v8}"(V[1]), "=&{v10}"(V[2]), "=&{v12}"(V[3]), "=&{v14}"(V[4]), "=&{v16}"(V[5]),
           "=&{v18}"(V[6]), "=&{v20}"(V[7]), "=&{v22}"(V[8])
         : [id] "v"(id)
         : "v6", "v7", "v11", "v13", "v15", "v17", "v19", "v21", "v23", "s58", "s59");
     return mn;
+}
+
+// ---- the id filter (basis_filter.h) -----------------------------------------
+// The table waits in device memory; every workgroup copies it into LDS once,
+// before its first trip (filter_load), and an id's test is one v_and (the
+// entry's byte address), one ds_read_b32 and one v_xor: filter_diff(id) is
+// below basis_filter::WINDOW iff the id is a candidate.
+static __device__ const basis_filter::Table FILTER_TABLE = basis_filter::TABLE;
+__device__ __forceinline__ uint32_t *filter_lds() {
+    __shared__ __attribute__((aligned(16))) uint32_t tab[basis_filter::SLOTS];
+    return tab;
+}
+__device__ __forceinline__ void filter_load() {
+    static_assert(basis_filter::SLOTS % (4 * BLOCK) == 0, "whole 16-byte copies per thread");
+    uint4 *dst = reinterpret_cast<uint4 *>(filter_lds());
+    const uint4 *src = reinterpret_cast<const uint4 *>(FILTER_TABLE.e);
+#pragma unroll
+    for (uint32_t i = 0; i < (uint32_t)basis_filter::SLOTS / 4; i += BLOCK) dst[i + threadIdx.x] = src[i + threadIdx.x];
+    __syncthreads();
+}
+__device__ __forceinline__ uint32_t filter_diff(uint32_t id) {
+    const char *tab = reinterpret_cast<const char *>(filter_lds());
+    return *reinterpret_cast<const uint32_t *>(tab + (id & basis_filter::KEY_MASK)) ^ id;
 }
 
 // powers of one id; returns a value below WRAP_BELOW if a lazy fold may have
@@ -717,13 +759,47 @@ template <class C> __device__ __forceinline__ void prio_exit() {
     if constexpr (C::PRIO == 2) __builtin_amdgcn_s_setprio(1);
 }
 
+// The filtered basis form (CfgBasis FILT).  A trip whose filter test found
+// nothing runs the lazy chain for its four ids and accumulates.  In a trip
+// with a candidate, the candidates are taken out first (basis_candidates):
+// where some lane's id is one, those lanes run the exact chain (always
+// congruent, so a candidate that is not wrong costs only this) while the
+// others feed id 0, whose powers are all 0, and the id is replaced by 0 for
+// the lazy pass that follows.  EXEC is full at every accumulation.
+template <class C>
+__device__ __forceinline__ void basis_one_lazy(Acc<8, 4, 3> &S, uint32_t id) {
+    uint32_t V[basis32::NE];
+    basis_chain(id, V);
+    prio_enter<C>();
+    if constexpr (C::PRIO != 0) __builtin_amdgcn_sched_barrier(0);
+    accumulate_basis<C>(S, V);
+    prio_exit<C>();
+}
+template <class C>
+__device__ __forceinline__ void basis_candidates(Acc<8, 4, 3> &S, uint32_t &id) {
+    const bool c = filter_diff(id) < basis_filter::WINDOW;
+    if (!__any(c)) return;
+    uint32_t V[basis32::NE];
+#pragma unroll
+    for (int i = 0; i < basis32::NE; ++i) V[i] = 0;
+    if (c) basis32::chain_exact(id, V);
+    prio_enter<C>();
+    accumulate_basis<C>(S, V);
+    prio_exit<C>();
+    id = c ? 0u : id;
+}
+
 // xb / xnext: an offset pass's cached x^base and the next pass's (Cfg XC)
 template <class C>
 __device__ __forceinline__ void one(Acc<C::NB, C::NA, C::ROWS> &S, uint32_t id, uint32_t base = 0, uint32_t xb = 0,
                                     uint32_t *xnext = nullptr) {
-    if constexpr (C::BASIS) {   // the same steps over the basis's nine values
+    if constexpr (C::BASIS && C::FILT) {   // a single id (head, tail): its own filter test
+        basis_candidates<C>(S, id);
+        basis_one_lazy<C>(S, id);
+        return;
+    } else if constexpr (C::BASIS) {   // the same steps over the basis's nine values
         uint32_t V[basis32::NE];
-        const uint32_t mn = basis_chain(id, V);
+        const uint32_t mn = basis_chain_min(id, V);
         prio_enter<C>();
         if constexpr (C::PRIO != 0) __builtin_amdgcn_sched_barrier(0);
         const bool w = mn < WRAP_BELOW;
@@ -770,7 +846,22 @@ __device__ __forceinline__ void two(Acc<C::NB, C::NA, C::ROWS> &S, uint32_t id0,
 template <class C>
 __device__ __forceinline__ void four(Acc<C::NB, C::NA, C::ROWS> &S, uint4 w, uint32_t base,
                                      uint4 xb = make_uint4(0, 0, 0, 0), uint4 *xn = nullptr) {
-    if constexpr (C::PAIR) {
+    if constexpr (C::BASIS && C::FILT) {
+        // one test per trip, before the chains: the smallest of the four differences
+        const uint32_t d0 = filter_diff(w.x), d1 = filter_diff(w.y), d2 = filter_diff(w.z), d3 = filter_diff(w.w);
+        const uint32_t d01 = d0 < d1 ? d0 : d1, d23 = d2 < d3 ? d2 : d3;
+        if (__builtin_expect(__any((d01 < d23 ? d01 : d23) < basis_filter::WINDOW), 0)) {
+            // rare: the candidates first, on their own (the other lanes feed id 0), then id 0 in their place
+            basis_candidates<C>(S, w.x);
+            basis_candidates<C>(S, w.y);
+            basis_candidates<C>(S, w.z);
+            basis_candidates<C>(S, w.w);
+        }
+        basis_one_lazy<C>(S, w.x);
+        basis_one_lazy<C>(S, w.y);
+        basis_one_lazy<C>(S, w.z);
+        basis_one_lazy<C>(S, w.w);
+    } else if constexpr (C::PAIR) {
         two<C>(S, w.x, w.y);
         two<C>(S, w.z, w.w);
     } else {
@@ -867,6 +958,7 @@ __device__ __forceinline__ void body_gen(const uint32_t *__restrict__ ids, uint6
     constexpr bool XI = (C::XC & 1) != 0, XO = (C::XC & 2) != 0;
     Acc<C::NB, C::NA, C::ROWS> S;
     clear<C>(S);
+    if constexpr (C::BASIS && C::FILT) filter_load();
     // The loops below leave two or three VGPRs to values that only the head,
     // the tail and finish() read.  gtid - threadIdx.x is the same in every
     // lane (both callers: a workgroup's first thread), so it and the wave's
@@ -1046,6 +1138,7 @@ __device__ __forceinline__ void body_dyn(const uint32_t *__restrict__ ids, uint6
     static_assert(!C::OFF && C::XC == 0, "dynamic chunks: plain single-pass configurations");
     Acc<C::NB, C::NA, C::ROWS> S;
     clear<C>(S);
+    if constexpr (C::BASIS && C::FILT) filter_load();
     // as body_gen: the wave's number waits in an SGPR and the thread's index
     // is rebuilt after the loops
     const uint32_t wave_s = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));

@@ -18,8 +18,9 @@ struct qk_knobs {
                            // resident round (bsgs.h body_dyn); 0: the static grid-stride form (tests compare
                            // both with the oracle; same-process A/Bs)
     int u32_basis = 1;     // 1: the u32 t = 31..32 encode takes its 32 powers from the nine-power basis (basis32.h:
-                           // 8 lazy products per id); 0: from the (8,4) grid (9) (tests compare both with the
-                           // oracle; same-process A/Bs)
+                           // 8 lazy products per id), the ids whose lazy chain is wrong looked up in a table
+                           // (basis_filter.h); 2: the same basis, those ids found by the minimum of each id's
+                           // products; 0: from the (8,4) grid (9) (tests compare all with the oracle; same-process A/Bs)
     int flow_hist = 32;   // per-flow batches of at most this many flows (and a table of <= 8192 slots) are
                            // grouped by per-workgroup slot histograms instead of the radix sort (0: never);
                            // 16 flows 2.76 vs 2.90 ms, 64: 3.17 vs 3.05, 1000: 5.80 vs 3.68

@@ -28,8 +28,10 @@
 //   * t = 31..32 (u32) — k_encode_u32_basis / k_encode_u32_basis_dyn (knob
 //     u32_basis, default 1): the same kernel bodies with the 32 powers from
 //     the nine-power basis of basis32.h, 8 lazy modmuls per id instead of the
-//     (8, 4) grid's 9 (bsgs.h CfgBasis).  u32_basis = 0 and the all-VALU
-//     fallback take the grid.
+//     (8, 4) grid's 9 (bsgs.h CfgBasis); the ids whose lazy chain is wrong
+//     are looked up in an LDS table once per trip (basis_filter.h).
+//     u32_basis = 2 finds them by the minimum of each id's products instead;
+//     u32_basis = 0 and the all-VALU fallback take the grid.
 //   * 14 <= t <= 80 (u64) — k_encode_u64_bsgs<NA,SG,F> (bsgs64.h): the
 //     same split with the babies/giants of a 256-id tile shared through LDS,
 //     each wave owning two babies' MAC rows (paired, at raised priority).
@@ -141,18 +143,20 @@ __global__ __launch_bounds__(BLOCK, (NB * NA == 32 ? 5 : NB * NA > 64 ? 2 : NB *
 // t = 31..32 from the nine-power basis (basis32.h, bsgs.h CfgBasis; knob
 // u32_basis): 8 lazy products per id instead of the (8,4) grid's 9, the same
 // accumulators, wrap counting and priorities.  Static and dynamic form.
-template <int PRIO = 1>
+// FILT 1: wrong ids by the table of basis_filter.h (16 KiB of LDS per
+// workgroup); 0: by the minimum of the products (knob u32_basis = 2).
+template <int PRIO = 1, int FILT = 1>
 __global__ __launch_bounds__(BLOCK, 5) void k_encode_u32_basis(const uint32_t *__restrict__ ids, uint64_t n,
                                                               uint32_t head, uint32_t T,
                                                               uint64_t *__restrict__ partials) {
-    bsgs::body<bsgs::CfgBasis<PRIO ? 4 : 0>>(ids, n, head, T, partials);
+    bsgs::body<bsgs::CfgBasis<PRIO ? 4 : 0, FILT>>(ids, n, head, T, partials);
 }
-template <int PRIO = 1>
+template <int PRIO = 1, int FILT = 1>
 __global__ __launch_bounds__(BLOCK, 5) void k_encode_u32_basis_dyn(const uint32_t *__restrict__ ids, uint64_t n,
                                                                   uint32_t head, uint32_t T,
                                                                   uint64_t *__restrict__ partials,
                                                                   const bsgs::DynArgs da) {
-    bsgs::body_dyn<bsgs::CfgBasis<PRIO ? 4 : 0>>(ids, n, head, T, partials, da);
+    bsgs::body_dyn<bsgs::CfgBasis<PRIO ? 4 : 0, FILT>>(ids, n, head, T, partials, da);
 }
 
 // Pass 0 of a multi-pass encode (powers 1..80) that also writes x^80 per id
@@ -982,10 +986,14 @@ static int enc32(qk_ctx *ctx, const uint32_t *ids, size_t n, uint32_t T, uint64_
 #define QK_BSGS_ROW(LO_, HI_, NB_, NA_, G_) \
     if (T >= LO_ && T <= HI_) return QK_BSGS(NB_, NA_, G_);
     if (sc_ok) {
-        if (T >= 31 && T <= 32 && ctx->knobs.u32_basis != 0)   // the nine-power basis (basis32.h)
-            return dyn ? run_encode_dyn(ctx, k_encode_u32_basis_dyn<1>, 32, ids, n, head, T, out, acc, s)
-                       : run_encode(ctx, k_encode_u32_basis<1>, 32, ids, n, head, T, (n + 3) / 4, BLOCK, out, acc, s,
-                                    0);
+        if (T >= 31 && T <= 32 && ctx->knobs.u32_basis == 1)   // the nine-power basis (basis32.h), ids filtered
+            return dyn ? run_encode_dyn(ctx, k_encode_u32_basis_dyn<1, 1>, 32, ids, n, head, T, out, acc, s)
+                       : run_encode(ctx, k_encode_u32_basis<1, 1>, 32, ids, n, head, T, (n + 3) / 4, BLOCK, out, acc,
+                                    s, 0);
+        if (T >= 31 && T <= 32 && ctx->knobs.u32_basis == 2)   // ... with the minimum tracked per product
+            return dyn ? run_encode_dyn(ctx, k_encode_u32_basis_dyn<1, 0>, 32, ids, n, head, T, out, acc, s)
+                       : run_encode(ctx, k_encode_u32_basis<1, 0>, 32, ids, n, head, T, (n + 3) / 4, BLOCK, out, acc,
+                                    s, 0);
         QK_U32_SHAPES(QK_BSGS_ROW)
         if (T > 80) return enc_passes(ctx, ids, n, head, T, out, acc, s);
     } else {
