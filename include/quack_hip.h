@@ -374,6 +374,63 @@ int qk_u32_decode_segments_device(qk_ctx *ctx, const uint8_t *diffs, const uint3
                                   size_t *n_hits, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Batched sender step: listen_for_quacks_power_sum (media_client.rs:223-323)
+ * for nseg flows whose sent logs stay in device memory.  Per flow g with a
+ * quACK (sidekick_amd/receiver.py QuackReceiver.on_quack is the same loop; the
+ * reset debounce stays with the caller):
+ *   peer.last_value == mine.last_value, compared as an Option (:233) -> IDLE:
+ *     mine_out = mine, drain 0, no hits.
+ *   idx = first position of segment g whose raw id equals peer.last_value
+ *     (:240-246; none when the peer has no last value).
+ *   mine1 = mine with log[off_g .. off_g + idx] inserted (:247-252): power sums
+ *     of id mod p added, count += idx + 1 (wrapping), last_value = that entry.
+ *   reset bits from mine1.count, peer.count and threshold in u32 arithmetic
+ *     (:257-261); any set -> action = their OR, mine_out = mine1 (the reference
+ *     inserts the prefix before it tests, and keeps it when the reset is
+ *     debounced), drain 0, no hits.
+ *   otherwise action = ADVANCED, drain = idx + 1, diff = mine1 - peer as
+ *     qk_u32_sub_assign (:295-296); the hits are what qk_u32_decode_host(diff,
+ *     segment, stop_at_last = 1) returns (:304-313; none when diff.count == 0),
+ *     and mine_out = mine1 with qk_u32_remove(id) once per hit (:318-322).
+ * A flow without a quACK (d_present[g] == 0) behaves like IDLE.
+ * ---------------------------------------------------------------------- */
+#define QK_SND_IDLE            0u  /* no quACK for the flow, or last_value unchanged (media_client.rs:233) */
+#define QK_SND_ADVANCED        1u  /* prefix inserted, decoded, drain[g] entries to drop (:295-322)       */
+#define QK_SND_RESET_REORDERED 2u  /* reset0: quack.last_value not in the log (:258)                      */
+#define QK_SND_RESET_RETX      4u  /* reset1: my count < quack count (:259)                               */
+#define QK_SND_RESET_EXCEEDS   8u  /* reset2: my count > quack count + threshold, u32 wrap (:260)         */
+/* d_mine, d_peer, d_mine_out: nseg qk_u32 records of qk_u32_size(threshold)
+ * bytes in device memory of ctx's GPU, row g for flow g; d_present: nseg
+ * device bytes or NULL (every flow has a quACK); d_log and host
+ * offsets[nseg + 1] as in qk_u32_decode_segments_device.  action, drain, hits,
+ * hit_offsets and n_hits are host memory; hits / hit_offsets as in
+ * qk_u32_decode_segments_device (global positions into d_log, ascending, CSR
+ * by segment).  Synchronous on `stream`.
+ * NULL ctx -> QK_E_INVAL before any other check; threshold 0 or > 1024 ->
+ * QK_E_THRESHOLD; a host pointer where a device one is required (or the
+ * reverse), decreasing offsets, or d_mine_out overlapping an input ->
+ * QK_E_INVAL; a record whose threshold field differs -> QK_E_MISMATCH;
+ * cap < total -> QK_E_CAPACITY with *n_hits and every output but hits written
+ * (a repeat with a larger cap gives the same outputs); nseg == 0 -> QK_OK with
+ * hit_offsets[0] = 0. */
+int qk_u32_sender_step_segments_device(qk_ctx *ctx, const uint8_t *d_mine, const uint8_t *d_peer,
+                                       const uint8_t *d_present, const uint32_t *d_log, const uint64_t *offsets,
+                                       size_t nseg, uint32_t threshold, uint8_t *d_mine_out, uint8_t *action,
+                                       uint64_t *drain, uint64_t *hits, size_t cap, uint64_t *hit_offsets,
+                                       size_t *n_hits, void *stream);
+/* seqno_ids.drain(..idx + 1) (media_client.rs:298,316) for all flows: segment
+ * g of the output is segment g of the input without its first drain[g]
+ * entries; offsets_out[nseg + 1] (host) is its CSR index, offsets_out[0] = 0.
+ * d_aux / d_aux_out: an optional parallel u32 array (the seqnos) moved alike,
+ * both NULL or both set.  drain[g] > the segment's length -> QK_E_INVAL;
+ * cap < the entries remaining -> QK_E_CAPACITY with offsets_out written; an
+ * output overlapping an input -> QK_E_INVAL.  Synchronous on `stream`. */
+int qk_u32_log_drain_segments_device(qk_ctx *ctx, const uint32_t *d_log, const uint32_t *d_aux,
+                                     const uint64_t *offsets, const uint64_t *drain, size_t nseg,
+                                     uint32_t *d_log_out, uint32_t *d_aux_out, size_t cap, uint64_t *offsets_out,
+                                     void *stream);
+
+/* ------------------------------------------------------------------------
  * Device-resident flow table: SidekickMulti's `senders: HashMap<AddrKey,
  * PowerSumQuackU32>` (sidekick_multi.rs:36,65-90) kept in HBM as a "flow
  * array": n qk_flow_key plus n qk_u32 records of qk_u32_size(threshold) bytes,

@@ -21,6 +21,12 @@ pub const QK_ID_OFFSET: usize = 63;
 pub const QK_BUFFER_SIZE: usize = 67;
 pub const QK_COMM_ID_BYTES: usize = 128;
 pub const QK_FLOW_JOIN_TILE: u32 = 2048;
+// qk_u32_sender_step_segments_device's action per flow (the reset bits may be ORed)
+pub const QK_SND_IDLE: u8 = 0;
+pub const QK_SND_ADVANCED: u8 = 1;
+pub const QK_SND_RESET_REORDERED: u8 = 2;
+pub const QK_SND_RESET_RETX: u8 = 4;
+pub const QK_SND_RESET_EXCEEDS: u8 = 8;
 
 pub const QK_OK: c_int = 0;
 pub const QK_E_INVAL: c_int = -1;
@@ -219,6 +225,17 @@ extern "C" {
                                          offsets: *const u64, nseg: usize, threshold: u32, stop_at_last: c_int,
                                          hits: *mut u64, cap: usize, hit_offsets: *mut u64, status: *mut int32_t,
                                          n_hits: *mut usize, stream: *mut c_void) -> c_int;
+
+    // batched sender step (media_client.rs:223-323 per flow) and the log drain (:298, :316)
+    pub fn qk_u32_sender_step_segments_device(ctx: *mut qk_ctx, d_mine: *const u8, d_peer: *const u8,
+                                              d_present: *const u8, d_log: *const u32, offsets: *const u64,
+                                              nseg: usize, threshold: u32, d_mine_out: *mut u8, action: *mut u8,
+                                              drain: *mut u64, hits: *mut u64, cap: usize, hit_offsets: *mut u64,
+                                              n_hits: *mut usize, stream: *mut c_void) -> c_int;
+    pub fn qk_u32_log_drain_segments_device(ctx: *mut qk_ctx, d_log: *const u32, d_aux: *const u32,
+                                            offsets: *const u64, drain: *const u64, nseg: usize,
+                                            d_log_out: *mut u32, d_aux_out: *mut u32, cap: usize,
+                                            offsets_out: *mut u64, stream: *mut c_void) -> c_int;
 
     // device-resident flow table
     pub fn qk_u32_flows_merge_device(ctx: *mut qk_ctx, d_keys_a: *const qk_flow_key, d_sk_a: *const u8, na: usize,

@@ -587,6 +587,81 @@ pub unsafe fn decode_segments_device(ctx: &Context, diffs: &[PowerSumQuackU32], 
     }
 }
 
+/// What one batched sender step returns ([`sender_step_segments_device`]), one
+/// entry per flow: `action` is `QK_SND_IDLE`, `QK_SND_ADVANCED` or the OR of the
+/// `QK_SND_RESET_*` bits, `drain` the log entries to drop
+/// ([`log_drain_segments_device`]), `hits` the positions into the grouped log to
+/// retransmit, ascending, with `hit_offsets` as their CSR index by flow.
+pub struct SenderStep {
+    pub action: Vec<u8>,
+    pub drain: Vec<u64>,
+    pub hits: Vec<u64>,
+    pub hit_offsets: Vec<u64>,
+}
+
+/// `listen_for_quacks_power_sum`'s work per quACK (`media_client.rs:233-322`) for
+/// `offsets.len() - 1` flows in one device pass: the log prefix up to the peer's
+/// last value inserted into mine, the three reset conditions, the decode of
+/// mine - peer against the flow's log, and the missing ids removed.  The reset
+/// debounce stays with the caller; on a reset bit `d_mine_out` holds the prefix
+/// insert.  `d_present` may be null (every flow has a quACK).
+///
+/// # Safety
+/// `d_mine`, `d_peer`, `d_mine_out` must each be `offsets.len() - 1` records of
+/// `qk_u32_size(threshold)` bytes in device memory of `ctx`'s GPU, `d_present`
+/// null or as many device bytes, `d_log` device memory holding
+/// `offsets.last()` ids; `d_mine_out` apart from the inputs.
+pub unsafe fn sender_step_segments_device(ctx: &Context, d_mine: *const u8, d_peer: *const u8, d_present: *const u8,
+                                          d_log: *const u32, offsets: &[u64], threshold: u32, d_mine_out: *mut u8,
+                                          stream: *mut c_void) -> Result<SenderStep> {
+    if offsets.is_empty() {
+        return Err(QuackError { status: ffi::QK_E_INVAL });
+    }
+    let n = offsets.len() - 1;
+    let mut cap = 1024usize.max(4 * n);
+    loop {
+        let mut action = vec![0u8; n.max(1)];
+        let mut drain = vec![0u64; n.max(1)];
+        let mut hits = vec![0u64; cap];
+        let mut hit_offsets = vec![0u64; n + 1];
+        let mut nh = 0usize;
+        let rc = ffi::qk_u32_sender_step_segments_device(ctx.raw, d_mine, d_peer, d_present, d_log, offsets.as_ptr(), n,
+                                                         threshold, d_mine_out, action.as_mut_ptr(),
+                                                         drain.as_mut_ptr(), hits.as_mut_ptr(), cap,
+                                                         hit_offsets.as_mut_ptr(), &mut nh, stream);
+        if rc == ffi::QK_E_CAPACITY && nh > cap {
+            cap = nh;
+            continue;
+        }
+        check(rc)?;
+        hits.truncate(nh);
+        action.truncate(n);
+        drain.truncate(n);
+        return Ok(SenderStep { action, drain, hits, hit_offsets });
+    }
+}
+
+/// `seqno_ids.drain(..idx + 1)` (`media_client.rs:298,316`) for all flows: flow
+/// g's log without its first `drain[g]` entries into `d_log_out` (room for `cap`
+/// entries), `d_aux` / `d_aux_out` (the seqnos; both null or both set) moved
+/// alike.  Returns the CSR offsets of the drained log.
+///
+/// # Safety
+/// `d_log` (and `d_aux`) must be device memory of `ctx`'s GPU holding
+/// `offsets.last()` entries, `d_log_out` (and `d_aux_out`) `cap` entries, the
+/// outputs apart from the inputs.
+pub unsafe fn log_drain_segments_device(ctx: &Context, d_log: *const u32, d_aux: *const u32, offsets: &[u64],
+                                        drain: &[u64], d_log_out: *mut u32, d_aux_out: *mut u32, cap: usize,
+                                        stream: *mut c_void) -> Result<Vec<u64>> {
+    if offsets.len() != drain.len() + 1 {
+        return Err(QuackError { status: ffi::QK_E_INVAL });
+    }
+    let mut offsets_out = vec![0u64; offsets.len()];
+    check(ffi::qk_u32_log_drain_segments_device(ctx.raw, d_log, d_aux, offsets.as_ptr(), drain.as_ptr(), drain.len(),
+                                                d_log_out, d_aux_out, cap, offsets_out.as_mut_ptr(), stream))?;
+    Ok(offsets_out)
+}
+
 /// A flow array in device memory: `n` keys, strictly ascending in byte order,
 /// and `n` `qk_u32` records of one threshold — `SidekickMulti`'s `senders`
 /// (`sidekick_multi.rs:36`) as [`encode_flows_device`]'s device output lays it

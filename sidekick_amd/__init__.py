@@ -2,8 +2,8 @@
 behind the C ABI in include/quack_hip.h).  See DESIGN.md."""
 from .quack import (  # noqa: F401
     CoefficientVector, Context, DeviceFlowQuacks, FlowQuacks, ModularInteger, PowerSumQuackU32, PowerSumQuackU64,
-    arithmetic, decode_segments, device_count, flows_diff, flows_lookup, flows_merge, get_context, roots,
-    to_coeffs_segments,
+    SenderStep, arithmetic, decode_segments, device_count, drain_segments, flows_diff, flows_lookup, flows_merge,
+    get_context, roots, sender_step, to_coeffs_segments,
 )
 from ._lib import P32, P64, QuackError, UndecodableError  # noqa: F401
 

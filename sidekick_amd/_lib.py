@@ -30,6 +30,12 @@ QK_E_PEER = -11
 P32 = 4294967291
 P64 = 18446744073709551557
 MAX_THRESHOLD = 1024
+# qk_u32_sender_step_segments_device's action per flow (QK_SND_*; the reset bits may be ORed)
+SND_IDLE = 0
+SND_ADVANCED = 1
+SND_RESET_REORDERED = 2
+SND_RESET_RETX = 4
+SND_RESET_EXCEEDS = 8
 FLOW_JOIN_TILE = 2048   # QK_FLOW_JOIN_TILE: keys of a and b together per work item of the flow-table join
 
 u8p = C.POINTER(C.c_uint8)
@@ -106,6 +112,9 @@ SIGNATURES = {
     "qk_u32_to_coeffs_segments_device": (C.c_int, [vp, vp, sz, C.c_uint32, u32p, u32p, C.POINTER(C.c_int32), vp]),
     "qk_u32_decode_segments_device": (C.c_int, [vp, vp, vp, u64p, sz, C.c_uint32, C.c_int, u64p, sz, u64p,
                                                 C.POINTER(C.c_int32), szp, vp]),
+    "qk_u32_sender_step_segments_device": (C.c_int, [vp, vp, vp, vp, vp, u64p, sz, C.c_uint32, vp, u8p, u64p, u64p,
+                                                     sz, u64p, szp, vp]),
+    "qk_u32_log_drain_segments_device": (C.c_int, [vp, vp, vp, u64p, u64p, sz, vp, vp, sz, u64p, vp]),
     "qk_u32_flows_merge_device": (C.c_int, [vp, vp, vp, sz, vp, vp, sz, C.c_uint32, C.c_uint32, vp, vp, vp, sz, szp,
                                             vp]),
     "qk_u32_flows_diff_device": (C.c_int, [vp, vp, vp, sz, vp, vp, sz, C.c_uint32, vp, szp, vp]),

@@ -190,6 +190,7 @@ int warm_packets(hipStream_t s);
 int warm_flows(hipStream_t s);
 int warm_segments(hipStream_t s);
 int warm_segdecode(hipStream_t s);
+int warm_sender(hipStream_t s);
 int warm_flowtable(hipStream_t s);
 int warm_comm(hipStream_t s);
 

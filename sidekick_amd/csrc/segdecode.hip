@@ -28,6 +28,7 @@
 
 #include "ctx.h"
 #include "field.h"
+#include "segdecode.h"
 #include "segments.h"
 
 namespace qk {
@@ -35,25 +36,6 @@ namespace qk {
 QK_WARM_KERNEL(segdecode)
 
 static_assert(sizeof(qk_u32) == 16, "qk_u32 header is 4 words");
-
-constexpr int SD_BLOCK = 256;
-constexpr uint32_t SD_ITEM = QK_SEG_DECODE_ITEM;   // log entries per work item
-constexpr uint32_t SD_WORDS = SD_ITEM / 64;        // hit-mask words per work item
-static_assert(SD_ITEM % SD_BLOCK == 0 && SD_WORDS <= 64, "k_seg_hit_write: one lane per mask word");
-// LDS words for the coefficient rows of one packed work item: a run of short
-// segments ends after SD_COEF_WORDS / T segments (at most SD_MAXSEG)
-constexpr uint32_t SD_COEF_WORDS = QK_SEG_DECODE_COEF_WORDS;
-constexpr uint32_t SD_MAXSEG = QK_SEG_DECODE_MAXSEG;
-
-struct SdItem {
-    uint64_t lo;     // first log position
-    uint32_t n;      // entries, 1..SD_ITEM
-    uint32_t seg0;   // first segment
-    uint32_t nseg;   // segments (1: possibly a slice of a long one)
-    uint32_t pad;
-};
-
-inline uint32_t sd_maxseg(uint32_t T) { return std::max(1u, std::min(SD_MAXSEG, SD_COEF_WORDS / T)); }
 
 // ------------------------------------------------------------------ Newton
 // c[i] = -(S[i] + sum_{j<i} S[j] c[i-j-1]) / (i+1), i = 0..d-1 (host.cpp:368).
@@ -109,26 +91,6 @@ __global__ __launch_bounds__(SD_BLOCK) void k_seg_newton(const uint32_t *__restr
 }
 
 // --------------------------------------------------------------- root test
-// the item's segment boundaries, relative to its first entry and clamped to
-// the item, into so[0 .. nseg]
-__device__ __forceinline__ void sd_stage_offsets(const SdItem &it, const uint64_t *__restrict__ offs, uint32_t *so) {
-    for (uint32_t k = threadIdx.x; k <= it.nseg; k += SD_BLOCK) {
-        const uint64_t o = offs[(uint64_t)it.seg0 + k];
-        so[k] = o <= it.lo ? 0u : o - it.lo >= it.n ? it.n : (uint32_t)(o - it.lo);
-    }
-}
-// the segment (relative to seg0) of entry i of the item: the last r with
-// so[r] <= i, so an empty segment never owns an entry
-__device__ __forceinline__ uint32_t sd_segment_of(const uint32_t *so, uint32_t nseg, uint32_t i) {
-    uint32_t lo = 0, hi = nseg;   // so[lo] <= i < so[hi]
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (so[mid] <= i) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // maxseg: the most segments any item of the launch holds (sizes the LDS).
 // LDS: so[maxseg + 1], sdeg[maxseg], sstop[maxseg], suse[maxseg], then the
 // coefficient rows, T + 1 words apart (lanes of different segments read
@@ -304,15 +266,6 @@ static int sd_inverses(qk_ctx *ctx, hipStream_t s) {
     return QK_OK;
 }
 
-// per-segment device buffers, carved from the context's per-flow arena
-struct SdSeg {
-    uint32_t *rec = nullptr;   // the records (the caller's, when they are device memory)
-    uint32_t *coef = nullptr, *deg = nullptr, *segcnt = nullptr;
-    int32_t *status = nullptr;
-    uint64_t *offs = nullptr, *total = nullptr;
-    unsigned long long *stop = nullptr;
-};
-
 static void sd_carve(Carve &cv, SdSeg &b, size_t nseg, uint32_t T, bool host_rec, bool decode) {
     if (host_rec) b.rec = cv.take<uint32_t>(nseg * (4 + T));
     b.coef = cv.take<uint32_t>(nseg * T);
@@ -352,6 +305,7 @@ static int sd_newton(qk_ctx *ctx, const uint8_t *diffs, bool host_rec, size_t ns
     return hipGetLastError() == hipSuccess ? QK_OK : QK_E_HIP;
 }
 
+
 // long segments cut into items of SD_ITEM entries; runs of whole short
 // segments packed up to SD_ITEM entries and sd_maxseg(T) segments
 static std::vector<SdItem> sd_items(const uint64_t *offs, size_t nseg, uint32_t T) {
@@ -374,9 +328,74 @@ static std::vector<SdItem> sd_items(const uint64_t *offs, size_t nseg, uint32_t 
     return items;
 }
 
-static int sd_check(qk_ctx *ctx, uint32_t threshold) {
+int sd_check(qk_ctx *ctx, uint32_t threshold) {
     if (!ctx) return QK_E_INVAL;
     if (threshold == 0 || threshold > QK_MAX_THRESHOLD) return QK_E_THRESHOLD;
+    return QK_OK;
+}
+
+void sd_plan(SdPlan &p, const uint64_t *offsets, size_t nseg, uint32_t T, size_t cap) {
+    p.items = sd_items(offsets, nseg, T);
+    p.maxseg = 1;   // the LDS of a launch follows its fullest item, not the packing limit
+    for (const SdItem &it : p.items) p.maxseg = std::max(p.maxseg, it.nseg);
+    p.n = offsets[nseg] - offsets[0];
+    p.hcap = std::min<uint64_t>(cap, p.n);
+}
+
+void sd_carve_plan(Carve &seg, Carve &item, SdPlan &p, size_t nseg, uint32_t T, bool host_rec) {
+    const size_t ni = p.items.size();
+    sd_carve(seg, p.b, nseg, T, host_rec, true);
+    p.d_mask = item.take<uint64_t>(ni * SD_WORDS);
+    p.d_base = item.take<uint64_t>(ni);
+    p.d_icnt = item.take<uint32_t>(ni);
+    p.d_hit = item.take<uint64_t>(p.hcap);
+}
+
+int sd_upload(qk_ctx *ctx, SdPlan &p, const uint64_t *offsets, size_t nseg, hipStream_t s) {
+    const size_t ni = p.items.size();
+    if (ni) {
+        if (int e = ensure_items(ctx, ni * sizeof(SdItem))) return e;
+        memcpy(ctx->h_items, p.items.data(), ni * sizeof(SdItem));
+    }
+    p.d_items = (const SdItem *)ctx->h_items_dev;
+    if (hipMemcpyAsync(p.b.offs, offsets, (nseg + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemsetAsync(p.b.stop, 0xFF, nseg * 8, s) != hipSuccess ||
+        hipMemsetAsync(p.b.segcnt, 0, nseg * 4, s) != hipSuccess || hipMemsetAsync(p.b.total, 0, 8, s) != hipSuccess)
+        return QK_E_HIP;
+    return QK_OK;
+}
+
+int sd_enqueue(qk_ctx *ctx, SdPlan &p, const uint8_t *diffs, bool host_rec, const uint32_t *d_log, size_t nseg,
+               uint32_t T, int stop_at_last, hipStream_t s) {
+    if (int e = sd_newton(ctx, diffs, host_rec, nseg, T, p.b, s)) return e;
+    const size_t ni = p.items.size();
+    if (!ni) return QK_OK;
+    const SdSeg &b = p.b;
+    const uint32_t maxseg = p.maxseg;
+    const size_t lds_rt = ((size_t)maxseg * 4 + 1 + (size_t)maxseg * (T + 1)) * sizeof(uint32_t);
+    const size_t lds_cnt = ((size_t)maxseg + 1) * sizeof(uint32_t);
+    hipEvent_t e0 = prof_begin(ctx, s);
+    hipLaunchKernelGGL(k_seg_root_test, dim3((uint32_t)ni), dim3(SD_BLOCK), lds_rt, s, d_log, p.d_items, b.offs, b.rec,
+                       b.coef, b.deg, T, maxseg, stop_at_last ? 1 : 0, b.stop, p.d_mask);
+    prof_end(ctx, s, e0);
+    hipLaunchKernelGGL(k_seg_hit_count, dim3((uint32_t)ni), dim3(SD_BLOCK), lds_cnt, s, p.d_items, b.offs, maxseg,
+                       b.stop, p.d_mask, p.d_icnt, b.segcnt);
+    hipLaunchKernelGGL(k_seg_scan, dim3(1), dim3(SD_SCAN), 0, s, p.d_icnt, (uint32_t)ni, p.d_base, b.total);
+    hipLaunchKernelGGL(k_seg_hit_write, dim3((uint32_t)ni), dim3(64), 0, s, p.d_items, p.d_mask, p.d_base, p.d_hit,
+                       p.hcap);
+    return hipGetLastError() == hipSuccess ? QK_OK : QK_E_HIP;
+}
+
+int sd_collect(const SdPlan &p, const int32_t *status, const uint32_t *segcnt, uint64_t total, size_t nseg,
+               uint64_t *hits, size_t cap, uint64_t *hit_offsets, size_t *n_hits) {
+    for (size_t g = 0; g < nseg; ++g)
+        if (status[g] == QK_E_MISMATCH) return QK_E_MISMATCH;
+    hit_offsets[0] = 0;
+    for (size_t g = 0; g < nseg; ++g) hit_offsets[g + 1] = hit_offsets[g] + segcnt[g];
+    *n_hits = (size_t)total;
+    if (hit_offsets[nseg] != total) return QK_E_HIP;   // the two counts are kept by different kernels
+    if (total > cap) return QK_E_CAPACITY;
+    if (total) QK_HIP_TRY(hipMemcpy(hits, p.d_hit, total * 8, hipMemcpyDeviceToHost));
     return QK_OK;
 }
 
@@ -434,70 +453,28 @@ extern "C" int qk_u32_decode_segments_device(qk_ctx *ctx, const uint8_t *diffs, 
     hipStream_t s = pick_stream(ctx, stream);
     const uint32_t T = threshold;
     const bool host_rec = !is_device_ptr(diffs);
-    const std::vector<SdItem> items = sd_items(offsets, nseg, T);
-    const size_t ni = items.size();
-    uint32_t maxseg = 1;   // the LDS of a launch follows its fullest item, not the packing limit
-    for (const SdItem &it : items) maxseg = std::max(maxseg, it.nseg);
-    const uint64_t hcap = std::min<uint64_t>(cap, n);   // hit positions kept on the device
+    SdPlan p;
+    sd_plan(p, offsets, nseg, T, cap);
     // per-segment buffers in the per-flow arena, per-item ones in the per-packet arena
-    Carve probe{nullptr};
-    SdSeg b;
-    sd_carve(probe, b, nseg, T, host_rec, true);
-    if (int e = ensure_flow(ctx, 1, probe.off, s)) return e;
-    Carve cv{(char *)ctx->d_flow[1]};
-    sd_carve(cv, b, nseg, T, host_rec, true);
-    uint64_t *d_mask = nullptr, *d_base = nullptr, *d_hit = nullptr;
-    uint32_t *d_icnt = nullptr;
     for (int pass = 0; pass < 2; ++pass) {
-        Carve ci{pass ? (char *)ctx->d_flow[0] : nullptr};
-        d_mask = ci.take<uint64_t>(ni * SD_WORDS);
-        d_base = ci.take<uint64_t>(ni);
-        d_icnt = ci.take<uint32_t>(ni);
-        d_hit = ci.take<uint64_t>(hcap);
-        if (!pass)
+        Carve cs{pass ? (char *)ctx->d_flow[1] : nullptr}, ci{pass ? (char *)ctx->d_flow[0] : nullptr};
+        sd_carve_plan(cs, ci, p, nseg, T, host_rec);
+        if (!pass) {
+            if (int e = ensure_flow(ctx, 1, cs.off, s)) return e;
             if (int e = ensure_flow(ctx, 0, ci.off, s)) return e;
+        }
     }
-    if (ni)
-        if (int e = ensure_items(ctx, ni * sizeof(SdItem))) return e;
-    if (ni) memcpy(ctx->h_items, items.data(), ni * sizeof(SdItem));
-    const SdItem *d_items = (const SdItem *)ctx->h_items_dev;
-
-    int rc = sd_newton(ctx, diffs, host_rec, nseg, T, b, s);
-    if (!rc && (hipMemcpyAsync(b.offs, offsets, (nseg + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
-                hipMemsetAsync(b.stop, 0xFF, nseg * 8, s) != hipSuccess ||
-                hipMemsetAsync(b.segcnt, 0, nseg * 4, s) != hipSuccess ||
-                hipMemsetAsync(b.total, 0, 8, s) != hipSuccess))
-        rc = QK_E_HIP;
-    if (!rc && ni) {
-        const size_t lds_rt = ((size_t)maxseg * 4 + 1 + (size_t)maxseg * (T + 1)) * sizeof(uint32_t);
-        const size_t lds_cnt = ((size_t)maxseg + 1) * sizeof(uint32_t);
-        hipEvent_t e0 = prof_begin(ctx, s);
-        hipLaunchKernelGGL(k_seg_root_test, dim3((uint32_t)ni), dim3(SD_BLOCK), lds_rt, s, d_log, d_items, b.offs,
-                           b.rec, b.coef, b.deg, T, maxseg, stop_at_last ? 1 : 0, b.stop, d_mask);
-        prof_end(ctx, s, e0);
-        hipLaunchKernelGGL(k_seg_hit_count, dim3((uint32_t)ni), dim3(SD_BLOCK), lds_cnt, s, d_items, b.offs, maxseg,
-                           b.stop, d_mask, d_icnt, b.segcnt);
-        hipLaunchKernelGGL(k_seg_scan, dim3(1), dim3(SD_SCAN), 0, s, d_icnt, (uint32_t)ni, d_base, b.total);
-        hipLaunchKernelGGL(k_seg_hit_write, dim3((uint32_t)ni), dim3(64), 0, s, d_items, d_mask, d_base, d_hit, hcap);
-        if (hipGetLastError() != hipSuccess) rc = QK_E_HIP;
-    }
+    int rc = sd_upload(ctx, p, offsets, nseg, s);
+    if (!rc) rc = sd_enqueue(ctx, p, diffs, host_rec, d_log, nseg, T, stop_at_last, s);
     std::vector<uint32_t> segcnt(nseg);
     uint64_t total = 0;
-    if (!rc && (hipMemcpyAsync(status, b.status, nseg * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-                hipMemcpyAsync(segcnt.data(), b.segcnt, nseg * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
-                hipMemcpyAsync(&total, b.total, 8, hipMemcpyDeviceToHost, s) != hipSuccess))
+    if (!rc && (hipMemcpyAsync(status, p.b.status, nseg * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                hipMemcpyAsync(segcnt.data(), p.b.segcnt, nseg * 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                hipMemcpyAsync(&total, p.b.total, 8, hipMemcpyDeviceToHost, s) != hipSuccess))
         rc = QK_E_HIP;
     // the one wait for the kernels (the pinned items, the host records and
     // the offsets must outlive them); the hit copy after it is sized by `total`
     if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = QK_E_HIP;
     if (rc) return rc;
-    for (size_t g = 0; g < nseg; ++g)
-        if (status[g] == QK_E_MISMATCH) return QK_E_MISMATCH;
-    hit_offsets[0] = 0;
-    for (size_t g = 0; g < nseg; ++g) hit_offsets[g + 1] = hit_offsets[g] + segcnt[g];
-    *n_hits = (size_t)total;
-    if (hit_offsets[nseg] != total) return QK_E_HIP;   // the two counts are kept by different kernels
-    if (total > cap) return QK_E_CAPACITY;
-    if (total) QK_HIP_TRY(hipMemcpy(hits, d_hit, total * 8, hipMemcpyDeviceToHost));
-    return QK_OK;
+    return sd_collect(p, status, segcnt.data(), total, nseg, hits, cap, hit_offsets, n_hits);
 }

@@ -21,6 +21,9 @@ plus the batch entry points of the MI355X engine:
     to_coeffs_segments(..)   to_coeffs of one diff sketch per flow, one device pass.
     decode_segments(..)      decode_with_log of many (diff, log segment) pairs,
                              one device pass (the per-flow quACKs of SidekickMulti).
+    sender_step(..)          the sender loop of media_client.rs:233-322 for many
+                             flows: prefix insert, reset test, decode, removes.
+    drain_segments(..)       seqno_ids.drain(..idx+1) of every flow's log.
     flows_merge / flows_diff / flows_lookup, DeviceFlowQuacks
                              SidekickMulti's flow table as key-sorted arrays in
                              HBM: merge a batch, diff against a peer, look up.
@@ -36,12 +39,14 @@ import threading
 
 import numpy as np
 
-from ._lib import (P32, P64, QK_E_CAPACITY, QK_E_MISMATCH, QuackError, check, lib)
+from dataclasses import dataclass
+
+from ._lib import (P32, P64, QK_E_CAPACITY, QK_E_INVAL, QK_E_MISMATCH, QuackError, check, lib)
 
 __all__ = [
     "PowerSumQuackU32", "PowerSumQuackU64", "ModularInteger", "CoefficientVector",
     "arithmetic", "Context", "get_context", "device_count", "FlowQuacks",
-    "to_coeffs_segments", "decode_segments",
+    "to_coeffs_segments", "decode_segments", "sender_step", "drain_segments", "SenderStep",
     "flows_merge", "flows_diff", "flows_lookup", "DeviceFlowQuacks",
 ]
 
@@ -587,6 +592,144 @@ def decode_segments(diffs, log, offsets, stop_at_last: bool = False, ctx: Contex
         a, b = int(hoffs[g]), int(hoffs[g + 1])
         out.append((hits[a:b] - offs[g]).tolist())
     return out, [int(s) for s in status[:nseg]]
+
+
+@dataclass
+class SenderStep:
+    """What sender_step returns, one entry per flow."""
+    mine_out: object      # CUDA int32 record tensor [nseg, 4 + t]: my quACKs after the step
+    action: np.ndarray    # np.uint8: SND_IDLE, SND_ADVANCED, or the OR of the SND_RESET_* bits
+    drain: np.ndarray     # np.uint64: log entries to drop (drain_segments)
+    missing: list         # per flow, the segment-local positions to retransmit, ascending
+
+
+def _record_tensor(recs, what: str, ctx_box: list, ctx):
+    """`recs` as a CUDA int32 record tensor [nseg, 4 + t]: a device tensor as it
+    is, a list of PowerSumQuackU32 of one threshold uploaded.  The context is
+    resolved (ctx_box[0]) before the upload: with no device that raises
+    QK_E_NO_DEVICE."""
+    ptr, nseg, t, dev, keep = _segment_records(recs, None)
+    if dev is not None:
+        if ctx_box[0] is None:
+            ctx_box[0] = ctx or get_context(dev)
+        return recs, nseg, t
+    if nseg == 0:
+        raise ValueError(f"{what}: an empty list of sketches has no threshold; pass a record tensor")
+    if ctx_box[0] is None:
+        ctx_box[0] = ctx or get_context(0)
+    import torch
+    host = np.frombuffer(keep, dtype=np.int32, count=nseg * (4 + t)).reshape(nseg, 4 + t)
+    return torch.from_numpy(host.copy()).to(f"cuda:{ctx_box[0].device}"), nseg, t
+
+
+def sender_step(mine, peer, log, offsets, present=None, ctx: Context | None = None) -> SenderStep:
+    """listen_for_quacks_power_sum (media_client.rs:233-322; QuackReceiver.on_quack)
+    for a batch of flows in one device pass (qk_u32_sender_step_segments_device).
+    `mine` / `peer`: my quACK and the received one per flow, row g for flow g (a
+    list of PowerSumQuackU32 of one threshold, uploaded here, or a CUDA int32
+    record tensor [nseg, 4 + t]); `log` the sent ids grouped by flow (a CUDA
+    u32/int32 tensor, or a host array, uploaded), `offsets` nseg + 1 ints (CSR);
+    `present` nseg flags (a host sequence or a CUDA uint8 tensor), None when
+    every flow has a quACK.  Per flow: the prefix up to the first entry equal to
+    the peer's last value is inserted into mine, the three reset conditions are
+    tested (a reset keeps the prefix insert and decodes nothing), otherwise
+    mine - peer is decoded against the segment and every missing id removed
+    from mine.  The reset debounce stays with the caller."""
+    box = [None]
+    d_mine, nseg, t = _record_tensor(mine, "mine", box, ctx)
+    d_peer, npeer, tp = _record_tensor(peer, "peer", box, ctx)
+    if tp != t:
+        raise QuackError(QK_E_MISMATCH, "mine and peer of different thresholds")
+    if npeer != nseg:
+        raise ValueError("mine and peer must hold one record per flow")
+    ctx = box[0]
+    import torch
+    device = d_mine.device
+    if d_peer.device != device:
+        raise ValueError("mine and peer on different devices")
+    d_log = _device_array(log, 32)
+    if d_log is None:
+        log = torch.from_numpy(_host_array(log, 32).view(np.int32)).to(device)
+        d_log = _device_array(log, 32)
+    lptr, n, _, stream = d_log
+    offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64))
+    if len(offs) != nseg + 1:
+        raise ValueError("offsets must hold one entry more than mine")
+    if nseg and int(offs[-1]) > n:
+        raise ValueError("offsets run past the end of log")
+    d_present = None
+    if present is not None:
+        if isinstance(present, torch.Tensor):
+            if not (present.is_cuda and present.dtype in (torch.uint8, torch.bool) and present.is_contiguous()):
+                raise TypeError("present must be a contiguous CUDA uint8/bool tensor or a host sequence")
+            d_present = present
+        else:
+            d_present = torch.from_numpy(np.ascontiguousarray(np.asarray(present, dtype=bool)).view(np.uint8)).to(device)
+        if d_present.numel() != nseg:
+            raise ValueError("present must hold one flag per flow")
+    mine_out = torch.empty((nseg, 4 + t), dtype=torch.int32, device=device)
+    action = np.zeros(max(nseg, 1), dtype=np.uint8)
+    drain = np.zeros(max(nseg, 1), dtype=np.uint64)
+    hoffs = np.zeros(nseg + 1, dtype=np.uint64)
+    cap = max(1024, 4 * nseg)
+    while True:
+        hits = np.empty(max(cap, 1), dtype=np.uint64)
+        nh = C.c_size_t()
+        rc = lib().qk_u32_sender_step_segments_device(
+            ctx.handle, d_mine.data_ptr(), d_peer.data_ptr(), d_present.data_ptr() if d_present is not None else None,
+            lptr, offs.ctypes.data_as(C.POINTER(C.c_uint64)), nseg, t, mine_out.data_ptr(),
+            action.ctypes.data_as(C.POINTER(C.c_uint8)), drain.ctypes.data_as(C.POINTER(C.c_uint64)),
+            hits.ctypes.data_as(C.POINTER(C.c_uint64)), cap, hoffs.ctypes.data_as(C.POINTER(C.c_uint64)),
+            C.byref(nh), stream)
+        if rc == QK_E_CAPACITY:
+            cap = nh.value
+            continue
+        check(rc, "sender_step")
+        break
+    missing = []
+    for g in range(nseg):
+        a, b = int(hoffs[g]), int(hoffs[g + 1])
+        missing.append((hits[a:b] - offs[g]).tolist())
+    return SenderStep(mine_out, action[:nseg], drain[:nseg], missing)
+
+
+def drain_segments(log, offsets, drain, aux=None, ctx: Context | None = None):
+    """seqno_ids.drain(..idx+1) (media_client.rs:298,316) for all flows on the
+    device (qk_u32_log_drain_segments_device): segment g of the result is
+    segment g of `log` (a CUDA u32/int32 tensor grouped by flow, CSR `offsets`)
+    without its first drain[g] entries.  `aux`: an optional parallel tensor
+    (the seqnos), moved alike.  Returns (log_out, offsets_out) or (log_out,
+    offsets_out, aux_out)."""
+    offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64))
+    dr = np.ascontiguousarray(np.asarray(drain, dtype=np.uint64))
+    nseg = len(offs) - 1
+    if nseg < 0 or len(dr) != nseg:
+        raise ValueError("offsets must hold one entry more than drain")
+    lens = offs[1:] - offs[:-1]
+    if np.any(offs[1:] < offs[:-1]) or np.any(dr > lens):
+        raise QuackError(QK_E_INVAL, "drain_segments: drain[g] exceeds the segment's length")
+    d_log = _device_array(log, 32)
+    if d_log is None:
+        raise TypeError("log must be a CUDA u32/int32 tensor")
+    lptr, n, dev, stream = d_log
+    if nseg and int(offs[-1]) > n:
+        raise ValueError("offsets run past the end of log")
+    if aux is not None:
+        d_aux = _device_array(aux, 32)
+        if d_aux is None or d_aux[1] != n or aux.device != log.device:
+            raise TypeError("aux must be a CUDA u32/int32 tensor as long as log, on its device")
+    ctx = ctx or get_context(dev)
+    import torch
+    left = int((lens - dr).sum())
+    out = torch.empty((left,), dtype=log.dtype, device=log.device)
+    aux_out = torch.empty((left,), dtype=aux.dtype, device=log.device) if aux is not None else None
+    offs_out = np.zeros(nseg + 1, dtype=np.uint64)
+    check(lib().qk_u32_log_drain_segments_device(
+        ctx.handle, lptr, d_aux[0] if aux is not None and left else None, offs.ctypes.data_as(C.POINTER(C.c_uint64)),
+        dr.ctypes.data_as(C.POINTER(C.c_uint64)), nseg, out.data_ptr() if left else None,
+        aux_out.data_ptr() if aux is not None and left else None, left,
+        offs_out.ctypes.data_as(C.POINTER(C.c_uint64)), stream), "drain_segments")
+    return (out, offs_out) if aux is None else (out, offs_out, aux_out)
 
 
 def encode_flows(bufs, threshold: int, stride: int = 67, meta=None, my_addr=None, ctx: Context | None = None,
