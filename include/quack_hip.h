@@ -429,6 +429,36 @@ int qk_u32_log_drain_segments_device(qk_ctx *ctx, const uint32_t *d_log, const u
                                      const uint64_t *offsets, const uint64_t *drain, size_t nseg,
                                      uint32_t *d_log_out, uint32_t *d_aux_out, size_t cap, uint64_t *offsets_out,
                                      void *stream);
+/* seqno_ids.push((seqno, id)) (media_client.rs:110 for every packet sent,
+ * :318-322 for every retransmission) for a batch of n_new sent packets over
+ * nseg flows, with the drain of :298,316 in the same pass: segment g of the
+ * output is segment g of the input without its first drain[g] entries (drain
+ * == NULL: nothing is drained), followed by every new entry i with
+ * d_new_flow[i] == g in ascending i.  The batch arrives ungrouped, in send
+ * order; the placement is stable, so a flow's log stays in send order.
+ * d_aux / d_new_aux / d_aux_out: the optional parallel u32 array (the seqnos)
+ * moved alike; aux mode is d_aux_out != NULL, in which d_aux is required when
+ * the input holds any entry and d_new_aux when n_new > 0; outside it both must
+ * be NULL.  n_new == 0 (d_new_* may be NULL) is exactly the drain.  offsets,
+ * drain and offsets_out[nseg + 1] (offsets_out[0] = 0) are host memory, every
+ * d_* device memory of ctx's GPU, 4-byte aligned; cap counts entries of
+ * d_log_out (and d_aux_out).  The flow set is the caller's: a new flow is an
+ * empty segment, a flow without traffic keeps its place.  Synchronous on
+ * `stream`.
+ * NULL ctx -> QK_E_INVAL before any other check; nseg == 0 -> QK_OK with
+ * offsets_out[0] = 0 (QK_E_INVAL when n_new > 0); decreasing offsets, drain[g]
+ * > the segment's length, n_new or nseg >= 2^32, a host pointer where a device
+ * one is required or the reverse, an output range overlapping an input range
+ * or the other output -> QK_E_INVAL; a d_new_flow[i] >= nseg (found on the
+ * device) -> QK_E_INVAL before any output array is written, offsets_out then
+ * unspecified; cap < the entries of the result -> QK_E_CAPACITY with
+ * offsets_out fully written and no output array written (a repeat with a
+ * larger cap gives the same result). */
+int qk_u32_log_update_segments_device(qk_ctx *ctx, const uint32_t *d_log, const uint32_t *d_aux,
+                                      const uint64_t *offsets, const uint64_t *drain, size_t nseg,
+                                      const uint32_t *d_new_flow, const uint32_t *d_new_ids,
+                                      const uint32_t *d_new_aux, size_t n_new, uint32_t *d_log_out,
+                                      uint32_t *d_aux_out, size_t cap, uint64_t *offsets_out, void *stream);
 
 /* ------------------------------------------------------------------------
  * Device-resident flow table: SidekickMulti's `senders: HashMap<AddrKey,

@@ -236,6 +236,12 @@ extern "C" {
                                             offsets: *const u64, drain: *const u64, nseg: usize,
                                             d_log_out: *mut u32, d_aux_out: *mut u32, cap: usize,
                                             offsets_out: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn qk_u32_log_update_segments_device(ctx: *mut qk_ctx, d_log: *const u32, d_aux: *const u32,
+                                             offsets: *const u64, drain: *const u64, nseg: usize,
+                                             d_new_flow: *const u32, d_new_ids: *const u32,
+                                             d_new_aux: *const u32, n_new: usize, d_log_out: *mut u32,
+                                             d_aux_out: *mut u32, cap: usize, offsets_out: *mut u64,
+                                             stream: *mut c_void) -> c_int;
 
     // device-resident flow table
     pub fn qk_u32_flows_merge_device(ctx: *mut qk_ctx, d_keys_a: *const qk_flow_key, d_sk_a: *const u8, na: usize,

@@ -191,6 +191,7 @@ int warm_flows(hipStream_t s);
 int warm_segments(hipStream_t s);
 int warm_segdecode(hipStream_t s);
 int warm_sender(hipStream_t s);
+int warm_senderlog(hipStream_t s);
 int warm_flowtable(hipStream_t s);
 int warm_comm(hipStream_t s);
 

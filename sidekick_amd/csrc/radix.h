@@ -43,8 +43,10 @@ constexpr uint32_t R = 1u << DBITS;
 // The first pass's chunk histograms from the key array (the later passes
 // count from the digit bytes, k_rs_count8; the per-flow batch's by-slot sort
 // has its first pass counted by k_flow_extract).  chunk is a multiple of 4
-// and keys is 16-byte aligned (arena buffers).
-__global__ __launch_bounds__(256) void k_rs_count(const uint32_t *__restrict__ keys, uint64_t n, uint64_t chunk,
+// and keys is 16-byte aligned (arena buffers).  The two count kernels are no
+// templates: static, since more than one translation unit drives the sort
+// (flows.hip, senderlog.hip).
+static __global__ __launch_bounds__(256) void k_rs_count(const uint32_t *__restrict__ keys, uint64_t n, uint64_t chunk,
                                                   uint32_t shift, uint32_t mask, uint32_t nwg,
                                                   uint32_t *__restrict__ cnt) {
     __shared__ uint32_t h[R];
@@ -67,7 +69,7 @@ __global__ __launch_bounds__(256) void k_rs_count(const uint32_t *__restrict__ k
 // the same histogram from a byte per item: the digit the previous pass's
 // scatter wrote beside each item (k_rs_scatter nd_out), 16 per load — the
 // pass reads 1 byte per item instead of the 8 of a (key, value) pair
-__global__ __launch_bounds__(256) void k_rs_count8(const uint8_t *__restrict__ dig, uint64_t n, uint64_t chunk,
+static __global__ __launch_bounds__(256) void k_rs_count8(const uint8_t *__restrict__ dig, uint64_t n, uint64_t chunk,
                                                    uint32_t nwg, uint32_t *__restrict__ cnt) {
     __shared__ uint32_t h[R];
     for (uint32_t j = threadIdx.x; j < R; j += blockDim.x) h[j] = 0;

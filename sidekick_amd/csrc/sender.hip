@@ -35,6 +35,7 @@
 #include "field.h"
 #include "segdecode.h"
 #include "segments.h"
+#include "senderlog.h"
 
 namespace qk {
 
@@ -284,31 +285,7 @@ __global__ __launch_bounds__(SD_BLOCK) void k_snd_finish(const uint32_t *__restr
 }
 
 // ------------------------------------------------------------------ drain
-constexpr uint32_t DR_ITEM = 2048;   // entries per copy item, one wave each
-struct DrItem {
-    uint64_t src, dst;   // positions in the input / output arrays
-    uint32_t n, pad;
-};
-
-// n words src -> dst by one wave: 16 bytes per lane where the two addresses
-// share their alignment, a scalar head up to the first 16-byte boundary
-__device__ __forceinline__ void dr_copy(const uint32_t *__restrict__ src, uint32_t *__restrict__ dst, uint32_t n,
-                                        uint32_t lane) {
-    const uintptr_t a = (uintptr_t)src, b = (uintptr_t)dst;
-    if (((a ^ b) & 15) != 0) {
-        for (uint32_t i = lane; i < n; i += 64) dst[i] = src[i];
-        return;
-    }
-    const uint32_t h4 = (uint32_t)((16 - (a & 15)) & 15) / 4, head = h4 < n ? h4 : n;
-    if (lane < head) dst[lane] = src[lane];
-    const uint32_t nv = (n - head) / 4;
-    const uint4 *sv = reinterpret_cast<const uint4 *>(src + head);
-    uint4 *dv = reinterpret_cast<uint4 *>(dst + head);
-    for (uint32_t v = lane; v < nv; v += 64) dv[v] = sv[v];
-    const uint32_t done = head + 4 * nv;
-    if (done + lane < n) dst[done + lane] = src[done + lane];
-}
-
+// DR_ITEM, DrItem and dr_copy: senderlog.h (the log update moves its kept entries the same way)
 __global__ __launch_bounds__(SD_BLOCK) void k_log_drain(const DrItem *__restrict__ items, uint32_t nitems,
                                                         const uint32_t *__restrict__ log,
                                                         const uint32_t *__restrict__ aux, uint32_t *__restrict__ out,

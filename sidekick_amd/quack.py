@@ -24,6 +24,10 @@ plus the batch entry points of the MI355X engine:
     sender_step(..)          the sender loop of media_client.rs:233-322 for many
                              flows: prefix insert, reset test, decode, removes.
     drain_segments(..)       seqno_ids.drain(..idx+1) of every flow's log.
+    update_segments(..)      the same drain plus seqno_ids.push of a batch of sent
+                             packets, one pass over the device-resident log.
+    DeviceSenderLog          QuackReceiver for many flows: log, seqnos and my
+                             quACKs stay in HBM between send and on_quacks.
     flows_merge / flows_diff / flows_lookup, DeviceFlowQuacks
                              SidekickMulti's flow table as key-sorted arrays in
                              HBM: merge a batch, diff against a peer, look up.
@@ -47,6 +51,7 @@ __all__ = [
     "PowerSumQuackU32", "PowerSumQuackU64", "ModularInteger", "CoefficientVector",
     "arithmetic", "Context", "get_context", "device_count", "FlowQuacks",
     "to_coeffs_segments", "decode_segments", "sender_step", "drain_segments", "SenderStep",
+    "update_segments", "DeviceSenderLog", "SenderLogStep",
     "flows_merge", "flows_diff", "flows_lookup", "DeviceFlowQuacks",
 ]
 
@@ -730,6 +735,201 @@ def drain_segments(log, offsets, drain, aux=None, ctx: Context | None = None):
         aux_out.data_ptr() if aux is not None and left else None, left,
         offs_out.ctypes.data_as(C.POINTER(C.c_uint64)), stream), "drain_segments")
     return (out, offs_out) if aux is None else (out, offs_out, aux_out)
+
+
+def _u32_len(a, what: str) -> int:
+    try:
+        return int(a.numel()) if hasattr(a, "numel") else len(a)
+    except TypeError:
+        raise TypeError(f"{what} must be a CUDA u32/int32 tensor or a host array") from None
+
+
+def _u32_on_device(a, device, what: str):
+    """`a` as a contiguous CUDA int32/uint32 tensor: a CUDA tensor as it is, a
+    host array uploaded."""
+    import torch
+    if isinstance(a, torch.Tensor):
+        if _device_array(a, 32) is None or a.device != device:
+            raise TypeError(f"{what} must be a CUDA u32/int32 tensor on the log's device, or a host array")
+        return a
+    return torch.from_numpy(_host_array(a, 32).view(np.int32)).to(device)
+
+
+def update_segments(log, offsets, drain, new_flow, new_ids, aux=None, new_aux=None, ctx: Context | None = None):
+    """seqno_ids.push((seqno, id)) (media_client.rs:110, :318-322) for a batch of
+    sent packets, with the drain of :298,316 in the same pass over the
+    device-resident log (qk_u32_log_update_segments_device).  Segment g of the
+    result is segment g of `log` (grouped by flow, CSR `offsets`) without its
+    first drain[g] entries (`drain` None: nothing is drained), followed by the
+    new_ids[i] with new_flow[i] == g in ascending i: the batch is given
+    ungrouped, in send order, and a flow's log stays in send order.  `aux` /
+    `new_aux`: the optional parallel array (the seqnos), both or neither.
+    `log`, `aux` and the three new_* arrays are CUDA u32/int32 tensors, or host
+    arrays, which are uploaded.  Returns (log_out, offsets_out) or (log_out,
+    offsets_out, aux_out), as drain_segments does."""
+    offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64))
+    nseg = len(offs) - 1
+    if nseg < 0:
+        raise ValueError("offsets must hold at least one entry")
+    lens = offs[1:] - offs[:-1]
+    dr = None
+    if drain is not None:
+        dr = np.ascontiguousarray(np.asarray(drain, dtype=np.uint64))
+        if len(dr) != nseg:
+            raise ValueError("offsets must hold one entry more than drain")
+    if np.any(offs[1:] < offs[:-1]) or (dr is not None and np.any(dr > lens)):
+        raise QuackError(QK_E_INVAL, "update_segments: drain[g] exceeds the segment's length")
+    n_new = _u32_len(new_flow, "new_flow")
+    if _u32_len(new_ids, "new_ids") != n_new:
+        raise ValueError("new_flow and new_ids must be equally long")
+    if (aux is None) != (new_aux is None):
+        raise ValueError("aux and new_aux go together")
+    if new_aux is not None and _u32_len(new_aux, "new_aux") != n_new:
+        raise ValueError("new_flow and new_aux must be equally long")
+    import torch
+    if isinstance(log, torch.Tensor):
+        d_log = _device_array(log, 32)
+        ctx = ctx or get_context(d_log[2])
+    else:   # a host log is uploaded; with no device this raises QK_E_NO_DEVICE
+        ctx = ctx or get_context(0)
+        log = torch.from_numpy(_host_array(log, 32).view(np.int32)).to(f"cuda:{ctx.device}")
+        d_log = _device_array(log, 32)
+    lptr, n, _, stream = d_log
+    device = log.device
+    if nseg and int(offs[-1]) > n:
+        raise ValueError("offsets run past the end of log")
+    if aux is not None:
+        aux = _u32_on_device(aux, device, "aux")
+        if aux.numel() != n:
+            raise TypeError("aux must be as long as log")
+        new_aux = _u32_on_device(new_aux, device, "new_aux")
+    new_flow = _u32_on_device(new_flow, device, "new_flow")
+    new_ids = _u32_on_device(new_ids, device, "new_ids")
+    # the result's size is known here: no capacity retry
+    total = int(lens.sum()) - (int(dr.sum()) if dr is not None else 0) + n_new
+    out = torch.empty((total,), dtype=log.dtype, device=device)
+    aux_out = torch.empty((total,), dtype=aux.dtype, device=device) if aux is not None else None
+    offs_out = np.zeros(nseg + 1, dtype=np.uint64)
+    u64 = C.POINTER(C.c_uint64)
+    has_in = nseg > 0 and int(offs[-1]) > int(offs[0])
+    check(lib().qk_u32_log_update_segments_device(
+        ctx.handle, lptr if has_in else None, aux.data_ptr() if aux is not None and has_in and total else None,
+        offs.ctypes.data_as(u64), dr.ctypes.data_as(u64) if dr is not None else None, nseg,
+        new_flow.data_ptr() if n_new else None, new_ids.data_ptr() if n_new else None,
+        new_aux.data_ptr() if aux is not None and n_new else None, n_new, out.data_ptr() if total else None,
+        aux_out.data_ptr() if aux is not None and total else None, total, offs_out.ctypes.data_as(u64), stream),
+        "update_segments")
+    return (out, offs_out) if aux is None else (out, offs_out, aux_out)
+
+
+@dataclass
+class SenderLogStep:
+    """What DeviceSenderLog.on_quacks returns, one entry per flow."""
+    action: np.ndarray      # np.uint8: SND_IDLE, SND_ADVANCED, or the OR of the SND_RESET_* bits
+    send_reset: np.ndarray  # bool: the reset fired (UDP [0] to the proxy, media_client.rs:272)
+    reset_reason: list      # (reordered?, retx?, exceeds threshold?) per flow with reset bits, else ()
+    retransmit: list        # per flow, the seqnos of the missing entries, in log order
+
+
+class DeviceSenderLog:
+    """QuackReceiver (receiver.py; media_client.rs:205-325) for many flows, its
+    state in HBM between calls: flow g behaves exactly as a
+    QuackReceiver(threshold, reset_debounce_s) given the same on_send /
+    on_quack calls.  `log` / `seqnos` are CUDA int32 tensors grouped by flow
+    (host CSR `offsets`), `mine` the record tensor [nflows, 4 + t];
+    `last_quack_reset` (NaN: none) stays on the host.  A round is one send()
+    (one pass over the log: the drain the last on_quacks left pending and the
+    batch's push) and one on_quacks() (one sender step); the log never crosses
+    to the host."""
+
+    def __init__(self, threshold: int, nflows: int, reset_debounce_s: float = 0.1, device: int = 0):
+        self.threshold = int(threshold)
+        self.reset_debounce_s = reset_debounce_s
+        self._ctx = get_context(device)          # no device: QK_E_NO_DEVICE, nothing falls back
+        import torch
+        self._device = torch.device(f"cuda:{device}")
+        self._fresh = torch.from_numpy(
+            np.frombuffer(PowerSumQuackU32(self.threshold)._buf, dtype=np.int32).copy()).to(self._device)
+        self.log = torch.empty((0,), dtype=torch.int32, device=self._device)
+        self.seqnos = torch.empty((0,), dtype=torch.int32, device=self._device)
+        self.mine = torch.empty((0, 4 + self.threshold), dtype=torch.int32, device=self._device)
+        self.offsets = np.zeros(1, dtype=np.uint64)
+        self.last_quack_reset = np.zeros(0, dtype=np.float64)
+        self._pending = None                      # np.uint64 per flow: the drain not yet applied
+        self.add_flows(nflows)
+
+    @property
+    def nflows(self) -> int:
+        return len(self.offsets) - 1
+
+    def add_flows(self, k: int) -> None:
+        """k more flows, each with an empty log and a fresh quACK."""
+        import torch
+        k = int(k)
+        if k < 0:
+            raise ValueError("k must not be negative")
+        self.offsets = np.concatenate([self.offsets, np.full(k, self.offsets[-1], dtype=np.uint64)])
+        self.mine = torch.cat([self.mine, self._fresh.unsqueeze(0).expand(k, -1)]).contiguous()
+        self.last_quack_reset = np.concatenate([self.last_quack_reset, np.full(k, np.nan)])
+        if self._pending is not None:
+            self._pending = np.concatenate([self._pending, np.zeros(k, dtype=np.uint64)])
+
+    def _update(self, flow, seqno, ids) -> None:
+        self.log, self.offsets, self.seqnos = update_segments(
+            self.log, self.offsets, self._pending, flow, ids, aux=self.seqnos, new_aux=seqno, ctx=self._ctx)
+        self._pending = None
+
+    def send(self, flow, seqno, ids) -> None:
+        """on_send(seqno, id) on flow[i] for every i, in this order; applies a
+        pending drain in the same pass."""
+        n = _u32_len(flow, "flow")
+        if _u32_len(seqno, "seqno") != n or _u32_len(ids, "ids") != n:
+            raise ValueError("flow, seqno and ids must be equally long")
+        self._update(flow, seqno, ids)
+
+    def flush(self) -> None:
+        """Applies a pending drain alone."""
+        if self._pending is not None and self._pending.any():
+            empty = np.zeros(0, dtype=np.uint32)
+            self._update(empty, empty, empty)
+        self._pending = None
+
+    def on_quacks(self, peer, present=None, now: float = 0.0) -> SenderLogStep:
+        """on_quack(peer[g], now) on every flow g with present[g] (None: all):
+        one sender step, the reset debounce of receiver.py:86-94 on the host."""
+        import torch
+        from ._lib import SND_ADVANCED
+        self.flush()
+        nf = self.nflows
+        res = sender_step(self.mine, peer, self.log, self.offsets, present=present, ctx=self._ctx)
+        self.mine = res.mine_out
+        action = res.action.copy()
+        drain = res.drain.copy()
+        bits = (action & ~np.uint8(SND_ADVANCED)) != 0
+        last = self.last_quack_reset
+        with np.errstate(invalid="ignore"):
+            fired = bits & (np.isnan(last) | (now > last + self.reset_debounce_s))
+        if fired.any():                                                     # media_client.rs:267-276
+            idx = torch.from_numpy(np.flatnonzero(fired)).to(self._device)
+            self.mine[idx] = self._fresh
+            lens = self.offsets[1:] - self.offsets[:-1]
+            drain[fired] = lens[fired]
+            last[fired] = now
+        last[action == SND_ADVANCED] = np.nan                               # :280-283
+        self._pending = drain if drain.any() else None
+        reason = [((a & 2) != 0, (a & 4) != 0, (a & 8) != 0) if b else () for a, b in zip(action.tolist(), bits.tolist())]
+        # the seqnos at the hit positions: the only log values that cross to the host
+        counts = [len(m) for m in res.missing]
+        retransmit = [[] for _ in range(nf)]
+        if sum(counts):
+            pos = np.concatenate([np.asarray(m, dtype=np.int64) + int(self.offsets[g])
+                                  for g, m in enumerate(res.missing) if m])
+            vals = self.seqnos[torch.from_numpy(pos).to(self._device)].cpu().numpy().view(np.uint32).tolist()
+            at = 0
+            for g, c in enumerate(counts):
+                retransmit[g] = vals[at:at + c]
+                at += c
+        return SenderLogStep(action, fired, reason, retransmit)
 
 
 def encode_flows(bufs, threshold: int, stride: int = 67, meta=None, my_addr=None, ctx: Context | None = None,
