@@ -130,6 +130,12 @@ bool is_device_ptr(const void *p) {
     return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
 }
 
+int check_ctx_threshold(const qk_ctx *ctx, uint32_t threshold) {
+    if (!ctx) return QK_E_INVAL;
+    if (threshold == 0 || threshold > QK_MAX_THRESHOLD) return QK_E_THRESHOLD;
+    return QK_OK;
+}
+
 static bool is_pinned_host_ptr(const void *p) {
     hipPointerAttribute_t attr;
     if (hipPointerGetAttributes(&attr, p) != hipSuccess) {

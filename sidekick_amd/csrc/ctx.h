@@ -6,6 +6,7 @@
 #include <mutex>
 #include <vector>
 
+#include "argcheck.h"
 #include "quack_hip.h"
 
 // Per-context knobs (qk_ctx_set_knob).  Round 6 removed every knob that
@@ -208,6 +209,10 @@ int ensure_flow(qk_ctx *ctx, int which, size_t bytes, hipStream_t s);
 int ensure_stage(qk_ctx *ctx, size_t bytes);
 int ensure_items(qk_ctx *ctx, size_t bytes);
 bool is_device_ptr(const void *p);
+// a non-null, 4-byte aligned device pointer (ranges_overlap: argcheck.h)
+inline bool dev_words(const void *p) { return p && ((uintptr_t)p & 3) == 0 && is_device_ptr(p); }
+// QK_E_INVAL without a context, QK_E_THRESHOLD outside 1 .. QK_MAX_THRESHOLD (api.hip)
+int check_ctx_threshold(const qk_ctx *ctx, uint32_t threshold);
 hipEvent_t prof_begin(qk_ctx *ctx, hipStream_t s);
 void prof_end(qk_ctx *ctx, hipStream_t s, hipEvent_t begin);
 

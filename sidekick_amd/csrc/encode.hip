@@ -75,20 +75,8 @@ using bsgs::WAVES;
 using bsgs::shfl_xor_u64;
 
 // ------------------------------------------------------------------ u32
-// Power chain in t-form (field.h: tstep32): per power three v_mad_u64_u32,
-// one v_sub_u32 and one 64-bit accumulate; x and x5 = 5x are canonical.
-
-template <int K>
-__device__ __forceinline__ void chain32(uint64_t (&acc)[K], uint32_t start, uint32_t step) {
-    // start: any value < 2^32 (t-form with hi = 0); step canonical
-    const uint32_t step5 = times5_32(step);
-    uint64_t t = start;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        acc[k] += t;
-        if (k + 1 < K) t = tstep32p(t, step, step5, 0u);
-    }
-}
+// Power chains in t-form (field.h: tstep32, chain32, group_powers32); x and
+// x5 = 5x are canonical.
 
 // four independent ids in lockstep (ILP for the dependent modmul chains);
 // the four t-form values of a power are summed before the accumulate
@@ -182,21 +170,6 @@ __global__ __launch_bounds__(BLOCK, (NA > 6 ? 2 : NA > 5 ? 3 : 4)) void k_encode
     uint64_t *__restrict__ partials, const uint32_t *xin, uint32_t *xout) {
     bsgs::body<bsgs::Cfg<8, NA, SG, 1, 1, false, true, XC, false, PRIO ? 4 : 0>>(ids, n, head, T, partials, base, xin,
                                                                                  xout);
-}
-
-// lane j of a G-group: start = x^(j+1), step = x^G (square-and-multiply).
-template <int G>
-__device__ __forceinline__ void group_powers32(uint32_t x, int j, uint32_t &start, uint32_t &step) {
-    uint32_t b = x, r = 1;
-    const uint32_t e = (uint32_t)j + 1;
-#pragma unroll
-    for (int bit = 0; (1 << bit) <= G; ++bit) {
-        const uint32_t rb = mul32_lazy(r, b);
-        r = ((e >> bit) & 1) ? rb : r;
-        if ((1 << bit) < G) b = mul32_lazy(b, b);
-    }
-    start = r;
-    step = canon32(b); // after log2(G) squarings b = x^G; the chain needs it canonical
 }
 
 // Reduce per-lane accumulators to one partial per (power, block).

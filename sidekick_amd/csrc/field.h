@@ -151,6 +151,45 @@ QK_HD uint32_t times5_32(uint32_t x) {
     return a < r ? a : r;
 }
 
+// ---- power chains: G lanes per id, lane j the powers j+1, j+1+G, ... ------
+// lane j of a G-group (G a power of two, j < G): start == x^(j+1) (lazy),
+// step = x^G (canonical), by square-and-multiply.  x: any value < 2^32.
+template <int G>
+QK_HD void group_powers32(uint32_t x, int j, uint32_t &start, uint32_t &step) {
+    uint32_t b = x, r = 1;
+    const uint32_t e = (uint32_t)j + 1;
+#pragma unroll
+    for (int bit = 0; (1 << bit) <= G; ++bit) {
+        const uint32_t rb = mul32_lazy(r, b);
+        r = ((e >> bit) & 1) ? rb : r;
+        if ((1 << bit) < G) b = mul32_lazy(b, b);
+    }
+    start = r;
+    step = canon32(b); // after log2(G) squarings b = x^G; the chain needs it canonical
+}
+
+// acc[k] += start * step^k in t-form (tstep32): per power three
+// v_mad_u64_u32, one v_sub_u32 and one 64-bit accumulate.  start: any value
+// < 2^32 (t-form with hi = 0); step canonical.  Every term is < 6 * 2^32.
+template <int K>
+QK_HD void chain32(uint64_t (&acc)[K], uint32_t start, uint32_t step) {
+    const uint32_t step5 = times5_32(step);
+    uint64_t t = start;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        acc[k] += t;
+        if (k + 1 < K) t = tstep32p(t, step, step5, 0u);
+    }
+}
+
+// one id's chain of lane j of its G-group: acc[k] += x^(j + 1 + k G); x canonical
+template <int G, int K>
+QK_HD void group_chain32(uint64_t (&acc)[K], uint32_t x, int j) {
+    uint32_t start = x, step = x;
+    if constexpr (G > 1) group_powers32<G>(x, j, start, step);
+    chain32<K>(acc, start, step);
+}
+
 // Fold a 64-bit lazy accumulator (any value) to [0, 2^32), congruent.
 QK_HD uint32_t fold64_32(uint64_t a) {
     uint64_t t = (a >> 32) * C32 + (uint32_t)a;         // < 6*2^32

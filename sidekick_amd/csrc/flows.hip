@@ -665,96 +665,10 @@ static uint64_t next_pow2(uint64_t v) {
     while (c < v) c <<= 1;
     return c;
 }
-static int bit_width32(uint32_t v) { return v ? 32 - __builtin_clz(v) : 0; }
 
 } // namespace qk
 
 using namespace qk;
-
-// The grouping sort (radix.h): chunks of the packets, one per workgroup
-struct RsPlan {
-    uint32_t nwg;
-    uint64_t chunk;   // a multiple of 4
-};
-// wgpc workgroups per CU (at most: one per 4096 packets)
-static RsPlan rs_plan(const qk_ctx *ctx, uint64_t n, uint32_t wgpc) {
-    const uint32_t nwg = (uint32_t)std::max<uint64_t>(
-        1, std::min<uint64_t>((uint64_t)ctx->num_cus * wgpc, (n + 4095) / 4096));
-    return {nwg, (((n + nwg - 1) / nwg) + 3) & ~(uint64_t)3};
-}
-constexpr uint32_t RS_WGPC_MAX = 4;
-// per-digit chunk counts, their prefixes within each digit and the digit
-// totals (k_row_scan) for one sort at a time; dig: one byte per item, the
-// next pass's 8-bit digit written by the scatter
-struct RsScratch {
-    uint32_t *cnt, *base, *tot;
-    uint8_t *dig;
-    template <class Carver> void take(Carver &c, uint32_t nwg, uint64_t n) {
-        cnt = c.template take<uint32_t>((size_t)rsort::R * nwg);
-        base = c.template take<uint32_t>((size_t)rsort::R * nwg);
-        tot = c.template take<uint32_t>(rsort::R);
-        dig = c.template take<uint8_t>(n + 16);
-    }
-};
-// Stable sort of (key, val) by the low `bits` bits of key, 8 bits per pass,
-// ping-ponging between region X = (k0, v0) and region Y = (k1, v1); each
-// region must also hold n (key, value) pairs from k0 / k1 (arena layout: the
-// value array follows the key array).  The first pass reads two arrays, the
-// last writes two, the passes between use pair arrays.  Every scatter writes
-// the next pass's digit as a byte beside each item, so the later passes
-// count 1 byte per item (k_rs_count8) instead of 8.  Returns in `where` the
-// region holding the result: 1 = Y, 0 = X (an even number of passes).
-// plan: the chunking to use instead of rs_plan's (pre0: sc.cnt already holds
-// the first pass's counts for it — k_flow_extract's fused histogram; the
-// scratch must hold R x plan->nwg counts)
-template <int BLK, int K, uint32_t WGPC>
-static int rs_sort_k(const qk_ctx *ctx, uint32_t *k0, uint32_t *v0, uint32_t *k1, uint32_t *v1, uint64_t n, int bits,
-                     const RsScratch &sc, hipStream_t s, int &where, const RsPlan *plan = nullptr, bool pre0 = false) {
-    static_assert(WGPC <= RS_WGPC_MAX, "scratch is sized for RS_WGPC_MAX");
-    constexpr int D = rsort::DBITS;
-    where = 0;
-    if (n == 0 || bits <= 0) return QK_OK;
-    const RsPlan pl0 = plan ? *plan : rs_plan(ctx, n, WGPC);
-    // the digit byte stream needs 16-item chunks (k_rs_count8's loads)
-    const RsPlan pl = RsPlan{pl0.nwg, (pl0.chunk + 15) & ~(uint64_t)15};
-    const int passes = (bits + D - 1) / D;
-    const int dd = (bits + passes - 1) / passes;   // the digit width actually used (<= D): balanced passes
-    uint32_t *ki = k0, *vi = v0, *ko = k1, *vo = v1;
-    for (int q = 0; q < passes; ++q) {
-        const uint32_t shift = (uint32_t)(q * dd);
-        const int left = bits - q * dd;
-        const uint32_t mask = left >= dd ? (1u << dd) - 1 : (1u << left) - 1;
-        const bool ip = q > 0, op = q + 1 < passes;
-        if (q > 0)   // the previous scatter wrote this pass's digits as bytes
-            hipLaunchKernelGGL(rsort::k_rs_count8, dim3(pl.nwg), dim3(256), 0, s, sc.dig, n, pl.chunk, pl.nwg, sc.cnt);
-        else if (!pre0)
-            hipLaunchKernelGGL(rsort::k_rs_count, dim3(pl.nwg), dim3(256), 0, s, ki, n, pl.chunk, shift, mask, pl.nwg,
-                               sc.cnt);
-        if (hipGetLastError() != hipSuccess) return QK_E_HIP;
-        // digit-major counts -> each digit's chunk prefixes + the digit totals
-        // (the scatter scans the totals itself)
-        hipLaunchKernelGGL(rsort::k_row_scan<256>, dim3(1u << D), dim3(256), 0, s, sc.cnt, pl.nwg, sc.base, sc.tot);
-        if (hipGetLastError() != hipSuccess) return QK_E_HIP;
-        auto kern = ip ? (op ? rsort::k_rs_scatter<D, BLK, K, true, true> : rsort::k_rs_scatter<D, BLK, K, true, false>)
-                       : (op ? rsort::k_rs_scatter<D, BLK, K, false, true> : rsort::k_rs_scatter<D, BLK, K, false, false>);
-        // the next pass's digit as a byte beside each item
-        const uint32_t nshift = (uint32_t)((q + 1) * dd);
-        const int nleft = bits - (q + 1) * dd;
-        const uint32_t nmask = nleft >= dd ? (1u << dd) - 1 : (1u << (nleft > 0 ? nleft : 0)) - 1;
-        hipLaunchKernelGGL(kern, dim3(pl.nwg), dim3(BLK), 0, s, ki, vi, n, pl.chunk, shift, mask, pl.nwg, sc.base,
-                           sc.tot, ko, vo, op ? sc.dig : (uint8_t *)nullptr, nshift, nmask);
-        if (hipGetLastError() != hipSuccess) return QK_E_HIP;
-        std::swap(ki, ko);
-        std::swap(vi, vo);
-    }
-    where = passes % 2;
-    return QK_OK;
-}
-// the grouping sort: 256 threads x 16 items per sub-tile, 4 workgroups per CU
-static int rs_sort(const qk_ctx *ctx, uint32_t *k0, uint32_t *v0, uint32_t *k1, uint32_t *v1, uint64_t n, int bits,
-                   const RsScratch &sc, hipStream_t s, int &where, const RsPlan *plan = nullptr, bool pre0 = false) {
-    return rs_sort_k<256, 16, 4>(ctx, k0, v0, k1, v1, n, bits, sc, s, where, plan, pre0);
-}
 
 // k_flow_extract's chunking of pn packets: >= 4 tiles per workgroup, enough
 // workgroups to cover the chip (FLOW_WGPC workgroups per CU; 4, 6, 8, 12
@@ -774,7 +688,7 @@ extern "C" int qk_u32_encode_flows_device(qk_ctx *ctx, const uint8_t *d_bufs, si
                                           qk_pkt_stats *stats, void *stream) {
     if (!ctx || !n_flows || (n && !d_bufs)) return QK_E_INVAL;
     if (stride < QK_BUFFER_SIZE || stride > 512) return QK_E_INVAL;
-    if (threshold == 0 || threshold > QK_MAX_THRESHOLD) return QK_E_THRESHOLD;
+    if (int e = check_ctx_threshold(ctx, threshold)) return e;
     if (n >= (1ull << 32)) return QK_E_INVAL; // packet indices are u32
     *n_flows = 0;
     qk_pkt_stats st = {0, 0, 0, 0, -1};

@@ -398,21 +398,8 @@ __global__ __launch_bounds__(FT_BLOCK) void k_ft_lookup(const uint32_t *__restri
 }
 
 // --------------------------------------------------------------------- host
-static bool ft_overlap(const void *p, size_t pn, const void *q, size_t qn) {
-    if (!p || !q || !pn || !qn) return false;
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + qn && b < a + pn;
-}
 // a device array of `bytes` bytes, 4-byte aligned (an empty one may be anything)
-static bool ft_dev(const void *p, size_t bytes) {
-    if (!bytes) return true;
-    return p && ((uintptr_t)p & 3) == 0 && is_device_ptr(p);
-}
-static int ft_check(qk_ctx *ctx, uint32_t threshold) {
-    if (!ctx) return QK_E_INVAL;
-    if (threshold == 0 || threshold > QK_MAX_THRESHOLD) return QK_E_THRESHOLD;
-    return QK_OK;
-}
+static bool ft_dev(const void *p, size_t bytes) { return !bytes || dev_words(p); }
 static bool ft_vec(uint32_t T, const void *a, const void *b, const void *o) {
     return T % 4 == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)o) & 15) == 0;
 }
@@ -451,7 +438,7 @@ extern "C" int qk_u32_flows_merge_device(qk_ctx *ctx, const qk_flow_key *d_keys_
                                          uint32_t threshold, uint32_t frequency_pkts, qk_flow_key *d_keys_out,
                                          uint8_t *d_sk_out, uint8_t *d_due_out, size_t cap, size_t *n_out,
                                          void *stream) {
-    if (int e = ft_check(ctx, threshold)) return e;
+    if (int e = check_ctx_threshold(ctx, threshold)) return e;
     if (!n_out || na >= ((size_t)1 << 31) || nb >= ((size_t)1 << 31)) return QK_E_INVAL;
     *n_out = 0;
     const uint32_t T = threshold;
@@ -468,9 +455,9 @@ extern "C" int qk_u32_flows_merge_device(qk_ctx *ctx, const qk_flow_key *d_keys_
     const size_t outb[3] = {cap * 12, cap * rec, cap};
     for (int o = 0; o < 3; ++o) {
         for (int i = 0; i < 4; ++i)
-            if (ft_overlap(out[o], outb[o], in[i], inb[i])) return QK_E_INVAL;
+            if (ranges_overlap(out[o], outb[o], in[i], inb[i])) return QK_E_INVAL;
         for (int p = 0; p < o; ++p)
-            if (ft_overlap(out[o], outb[o], out[p], outb[p])) return QK_E_INVAL;
+            if (ranges_overlap(out[o], outb[o], out[p], outb[p])) return QK_E_INVAL;
     }
     const size_t N = na + nb;
     if (N == 0) return QK_OK;
@@ -524,7 +511,7 @@ extern "C" int qk_u32_flows_merge_device(qk_ctx *ctx, const qk_flow_key *d_keys_
 extern "C" int qk_u32_flows_diff_device(qk_ctx *ctx, const qk_flow_key *d_keys_a, const uint8_t *d_sk_a, size_t na,
                                         const qk_flow_key *d_keys_b, const uint8_t *d_sk_b, size_t nb,
                                         uint32_t threshold, uint8_t *d_diffs_out, size_t *n_matched, void *stream) {
-    if (int e = ft_check(ctx, threshold)) return e;
+    if (int e = check_ctx_threshold(ctx, threshold)) return e;
     if (!n_matched || na >= ((size_t)1 << 31) || nb >= ((size_t)1 << 31)) return QK_E_INVAL;
     *n_matched = 0;
     const uint32_t T = threshold;
@@ -534,8 +521,8 @@ extern "C" int qk_u32_flows_diff_device(qk_ctx *ctx, const qk_flow_key *d_keys_a
     if (!ft_dev(d_keys_a, na * 12) || !ft_dev(d_sk_a, na * rec) || !ft_dev(d_keys_b, nb * 12) ||
         !ft_dev(d_sk_b, nb * rec) || !ft_dev(d_diffs_out, na * rec))
         return QK_E_INVAL;
-    if (ft_overlap(d_diffs_out, na * rec, d_keys_a, na * 12) || ft_overlap(d_diffs_out, na * rec, d_sk_a, na * rec) ||
-        ft_overlap(d_diffs_out, na * rec, d_keys_b, nb * 12) || ft_overlap(d_diffs_out, na * rec, d_sk_b, nb * rec))
+    if (ranges_overlap(d_diffs_out, na * rec, d_keys_a, na * 12) || ranges_overlap(d_diffs_out, na * rec, d_sk_a, na * rec) ||
+        ranges_overlap(d_diffs_out, na * rec, d_keys_b, nb * 12) || ranges_overlap(d_diffs_out, na * rec, d_sk_b, nb * rec))
         return QK_E_INVAL;
     const size_t N = na + nb;
     if (N == 0) return QK_OK;
@@ -585,7 +572,7 @@ extern "C" int qk_u32_flows_diff_device(qk_ctx *ctx, const qk_flow_key *d_keys_a
 extern "C" int qk_u32_flows_lookup_device(qk_ctx *ctx, const qk_flow_key *d_keys, const uint8_t *d_sk, size_t n,
                                           uint32_t threshold, const qk_flow_key *keys, size_t nk, uint8_t *sketches,
                                           uint8_t *found, void *stream) {
-    if (int e = ft_check(ctx, threshold)) return e;
+    if (int e = check_ctx_threshold(ctx, threshold)) return e;
     if (n >= ((size_t)1 << 31) || nk >= ((size_t)1 << 31)) return QK_E_INVAL;
     if (nk == 0) return QK_OK;
     if (!keys || !sketches || !found) return QK_E_INVAL;

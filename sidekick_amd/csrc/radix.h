@@ -1,6 +1,7 @@
 // radix.h — the per-flow batch's grouping sort (flows.hip):
 // a stable LSD radix sort of (u32 key, u32 value) pairs over the low `bits`
 // bits of the key, 8-bit digits, one chunked counting scatter per digit.
+// The kernels, then the host driver (rs_sort_k) at the end.
 //
 // It replaces sidekick_multi.rs:65-90's per-packet HashMap update for a batch
 // of 1e8 packets: grouping the ids by flow slot, packet order kept inside a
@@ -32,7 +33,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <type_traits>
+#include <utility>
+
+#include "ctx.h"
 
 namespace qk {
 namespace rsort {
@@ -325,4 +330,102 @@ __global__ __launch_bounds__(BLK) void k_rs_scatter(const uint32_t *__restrict__
 }
 
 } // namespace rsort
+
+// ------------------------------------------------------------------- host
+// The sort's driver, for every translation unit that sorts (flows.hip: the
+// per-flow batch's grouping sorts; senderlog.hip: the batch of new entries by
+// flow index).
+inline int bit_width32(uint32_t v) { return v ? 32 - __builtin_clz(v) : 0; }
+
+// chunks of the items, one per workgroup
+struct RsPlan {
+    uint32_t nwg;
+    uint64_t chunk;   // a multiple of 4
+};
+// wgpc workgroups per CU (at most: one per 4096 items)
+inline RsPlan rs_plan(const qk_ctx *ctx, uint64_t n, uint32_t wgpc) {
+    const uint32_t nwg = (uint32_t)std::max<uint64_t>(
+        1, std::min<uint64_t>((uint64_t)ctx->num_cus * wgpc, (n + 4095) / 4096));
+    return {nwg, (((n + nwg - 1) / nwg) + 3) & ~(uint64_t)3};
+}
+constexpr uint32_t RS_WGPC_MAX = 4;
+// per-digit chunk counts, their prefixes within each digit and the digit
+// totals (k_row_scan) for one sort at a time; dig: one byte per item, the
+// next pass's 8-bit digit written by the scatter
+struct RsScratch {
+    uint32_t *cnt, *base, *tot;
+    uint8_t *dig;
+    template <class Carver> void take(Carver &c, uint32_t nwg, uint64_t n) {
+        cnt = c.template take<uint32_t>((size_t)rsort::R * nwg);
+        base = c.template take<uint32_t>((size_t)rsort::R * nwg);
+        tot = c.template take<uint32_t>(rsort::R);
+        dig = c.template take<uint8_t>(n + 16);
+    }
+};
+// Stable sort of (key, val) by the low `bits` bits of key, 8 bits per pass,
+// ping-ponging between region X = (k0, v0) and region Y = (k1, v1); each
+// region must also hold n (key, value) pairs from k0 / k1 (arena layout: the
+// value array follows the key array).  The first pass reads two arrays, the
+// last writes two, the passes between use pair arrays.  Every scatter writes
+// the next pass's digit as a byte beside each item, so the later passes
+// count 1 byte per item (k_rs_count8) instead of 8.  Returns in `where` the
+// region holding the result: 1 = Y, 0 = X (an even number of passes).
+// plan: the chunking to use instead of rs_plan's (pre0: sc.cnt already holds
+// the first pass's counts for it — k_flow_extract's or k_sl_count's fused
+// histogram; the scratch must hold R x plan->nwg counts).
+// first_keys: the first pass reads its keys from there instead of k0 — a
+// caller's array, never written; k0 stays region X's key half, which later
+// passes may write.
+template <int BLK, int K, uint32_t WGPC>
+int rs_sort_k(const qk_ctx *ctx, uint32_t *k0, uint32_t *v0, uint32_t *k1, uint32_t *v1, uint64_t n, int bits,
+              const RsScratch &sc, hipStream_t s, int &where, const RsPlan *plan = nullptr, bool pre0 = false,
+              const uint32_t *first_keys = nullptr) {
+    static_assert(WGPC <= RS_WGPC_MAX, "scratch is sized for RS_WGPC_MAX");
+    constexpr int D = rsort::DBITS;
+    where = 0;
+    if (n == 0 || bits <= 0) return QK_OK;
+    const RsPlan pl0 = plan ? *plan : rs_plan(ctx, n, WGPC);
+    // the digit byte stream needs 16-item chunks (k_rs_count8's loads)
+    const RsPlan pl = RsPlan{pl0.nwg, (pl0.chunk + 15) & ~(uint64_t)15};
+    const int passes = (bits + D - 1) / D;
+    const int dd = (bits + passes - 1) / passes;   // the digit width actually used (<= D): balanced passes
+    uint32_t *ki = k0, *vi = v0, *ko = k1, *vo = v1;
+    for (int q = 0; q < passes; ++q) {
+        const uint32_t shift = (uint32_t)(q * dd);
+        const int left = bits - q * dd;
+        const uint32_t mask = left >= dd ? (1u << dd) - 1 : (1u << left) - 1;
+        const bool ip = q > 0, op = q + 1 < passes;
+        const uint32_t *keys = q == 0 && first_keys ? first_keys : ki;
+        if (q > 0)   // the previous scatter wrote this pass's digits as bytes
+            hipLaunchKernelGGL(rsort::k_rs_count8, dim3(pl.nwg), dim3(256), 0, s, sc.dig, n, pl.chunk, pl.nwg, sc.cnt);
+        else if (!pre0)
+            hipLaunchKernelGGL(rsort::k_rs_count, dim3(pl.nwg), dim3(256), 0, s, keys, n, pl.chunk, shift, mask, pl.nwg,
+                               sc.cnt);
+        if (hipGetLastError() != hipSuccess) return QK_E_HIP;
+        // digit-major counts -> each digit's chunk prefixes + the digit totals
+        // (the scatter scans the totals itself)
+        hipLaunchKernelGGL(rsort::k_row_scan<256>, dim3(1u << D), dim3(256), 0, s, sc.cnt, pl.nwg, sc.base, sc.tot);
+        if (hipGetLastError() != hipSuccess) return QK_E_HIP;
+        auto kern = ip ? (op ? rsort::k_rs_scatter<D, BLK, K, true, true> : rsort::k_rs_scatter<D, BLK, K, true, false>)
+                       : (op ? rsort::k_rs_scatter<D, BLK, K, false, true> : rsort::k_rs_scatter<D, BLK, K, false, false>);
+        // the next pass's digit as a byte beside each item
+        const uint32_t nshift = (uint32_t)((q + 1) * dd);
+        const int nleft = bits - (q + 1) * dd;
+        const uint32_t nmask = nleft >= dd ? (1u << dd) - 1 : (1u << (nleft > 0 ? nleft : 0)) - 1;
+        hipLaunchKernelGGL(kern, dim3(pl.nwg), dim3(BLK), 0, s, keys, vi, n, pl.chunk, shift, mask, pl.nwg, sc.base,
+                           sc.tot, ko, vo, op ? sc.dig : (uint8_t *)nullptr, nshift, nmask);
+        if (hipGetLastError() != hipSuccess) return QK_E_HIP;
+        std::swap(ki, ko);
+        std::swap(vi, vo);
+    }
+    where = passes % 2;
+    return QK_OK;
+}
+// the grouping sort: 256 threads x 16 items per sub-tile, 4 workgroups per CU
+inline int rs_sort(const qk_ctx *ctx, uint32_t *k0, uint32_t *v0, uint32_t *k1, uint32_t *v1, uint64_t n, int bits,
+                   const RsScratch &sc, hipStream_t s, int &where, const RsPlan *plan = nullptr, bool pre0 = false,
+                   const uint32_t *first_keys = nullptr) {
+    return rs_sort_k<256, 16, 4>(ctx, k0, v0, k1, v1, n, bits, sc, s, where, plan, pre0, first_keys);
+}
+
 } // namespace qk

@@ -94,6 +94,4 @@ int sd_enqueue(qk_ctx *ctx, SdPlan &p, const uint8_t *diffs, bool host_rec, cons
 int sd_collect(const SdPlan &p, const int32_t *status, const uint32_t *segcnt, uint64_t total, size_t nseg,
                uint64_t *hits, size_t cap, uint64_t *hit_offsets, size_t *n_hits);
 
-int sd_check(qk_ctx *ctx, uint32_t threshold);
-
 } // namespace qk

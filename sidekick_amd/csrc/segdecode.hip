@@ -328,12 +328,6 @@ static std::vector<SdItem> sd_items(const uint64_t *offs, size_t nseg, uint32_t 
     return items;
 }
 
-int sd_check(qk_ctx *ctx, uint32_t threshold) {
-    if (!ctx) return QK_E_INVAL;
-    if (threshold == 0 || threshold > QK_MAX_THRESHOLD) return QK_E_THRESHOLD;
-    return QK_OK;
-}
-
 void sd_plan(SdPlan &p, const uint64_t *offsets, size_t nseg, uint32_t T, size_t cap) {
     p.items = sd_items(offsets, nseg, T);
     p.maxseg = 1;   // the LDS of a launch follows its fullest item, not the packing limit
@@ -405,7 +399,7 @@ using namespace qk;
 
 extern "C" int qk_u32_to_coeffs_segments_device(qk_ctx *ctx, const uint8_t *diffs, size_t nseg, uint32_t threshold,
                                                 uint32_t *coeffs, uint32_t *degrees, int32_t *status, void *stream) {
-    if (int e = sd_check(ctx, threshold)) return e;
+    if (int e = check_ctx_threshold(ctx, threshold)) return e;
     if (nseg == 0) return QK_OK;
     if (!diffs || !coeffs || !degrees || !status || nseg > 0xFFFFFFFFull) return QK_E_INVAL;
     std::lock_guard<std::mutex> lk(ctx->mu);
@@ -436,7 +430,7 @@ extern "C" int qk_u32_decode_segments_device(qk_ctx *ctx, const uint8_t *diffs, 
                                              const uint64_t *offsets, size_t nseg, uint32_t threshold,
                                              int stop_at_last, uint64_t *hits, size_t cap, uint64_t *hit_offsets,
                                              int32_t *status, size_t *n_hits, void *stream) {
-    if (int e = sd_check(ctx, threshold)) return e;
+    if (int e = check_ctx_threshold(ctx, threshold)) return e;
     if (n_hits) *n_hits = 0;
     if (nseg == 0) {
         if (hit_offsets) hit_offsets[0] = 0;

@@ -28,21 +28,7 @@ static_assert(sizeof(qk_u32) == 16, "qk_u32 header is 4 words (k_seg_small write
 constexpr int SG_BLOCK = bsgs::BLOCK;
 constexpr int SG_WAVES = bsgs::WAVES;
 
-// lane j of a G-group: start = x^(j+1), step = x^G (canonical)
-template <int G>
-__device__ __forceinline__ void sg_group_powers(uint32_t x, int j, uint32_t &start, uint32_t &step) {
-    uint32_t b = x, r = 1;
-    const uint32_t e = (uint32_t)j + 1;
-#pragma unroll
-    for (int bit = 0; (1 << bit) <= G; ++bit) {
-        const uint32_t rb = mul32_lazy(r, b);
-        r = ((e >> bit) & 1) ? rb : r;
-        if ((1 << bit) < G) b = mul32_lazy(b, b);
-    }
-    start = r;
-    step = canon32(b);
-}
-
+// G lanes per id, lane j a chain of K powers j+1, j+1+G, ... (field.h group_chain32)
 template <int G, int K>
 __global__ __launch_bounds__(SG_BLOCK) void k_seg_encode(const uint32_t *__restrict__ ids,
                                                          const SegItem *__restrict__ items, uint32_t T,
@@ -53,19 +39,8 @@ __global__ __launch_bounds__(SG_BLOCK) void k_seg_encode(const uint32_t *__restr
 #pragma unroll
     for (int k = 0; k < K; ++k) acc[k] = 0;
     const int j = threadIdx.x % G;
-    for (uint64_t i = it.lo + threadIdx.x / G; i < it.hi; i += SG_BLOCK / G) {
-        const uint32_t x = canon32(ids[i]);
-        uint32_t start, step;
-        if constexpr (G == 1) { start = x; step = x; }
-        else sg_group_powers<G>(x, j, start, step);
-        const uint32_t step5 = times5_32(step);
-        uint64_t t = start;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            acc[k] += t;
-            if (k + 1 < K) t = tstep32p(t, step, step5, 0u);
-        }
-    }
+    for (uint64_t i = it.lo + threadIdx.x / G; i < it.hi; i += SG_BLOCK / G)
+        group_chain32<G, K>(acc, canon32(ids[i]), j);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
@@ -327,7 +302,7 @@ using namespace qk;
 extern "C" int qk_u32_encode_segments_device(qk_ctx *ctx, const uint32_t *d_ids, const uint64_t *offsets,
                                              size_t nseg, uint32_t threshold, uint8_t *sketches, void *stream) {
     if (!ctx || !offsets || (nseg && !sketches)) return QK_E_INVAL;
-    if (threshold == 0 || threshold > QK_MAX_THRESHOLD) return QK_E_THRESHOLD;
+    if (int e = check_ctx_threshold(ctx, threshold)) return e;
     if (nseg == 0) return QK_OK;
     std::vector<uint64_t> offs(offsets, offsets + nseg + 1);
     for (size_t g = 0; g < nseg; ++g)

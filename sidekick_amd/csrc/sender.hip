@@ -23,7 +23,6 @@
 //                    diff records (segdecode.hip), stop_at_last = 1
 //   k_snd_remove     every surviving hit bit adds p - x^k to its segment's row
 //   k_snd_finish     the rows of the segments with hits back into mine_out
-//   k_log_drain      seqno_ids.drain(..idx+1) for all flows: one copy kernel
 // Every sum is an integer sum of values below 2^32 in a 64-bit word, folded
 // once at the end: exact and independent of the order of the atomics.
 #include <string.h>
@@ -31,11 +30,11 @@
 #include <algorithm>
 #include <vector>
 
+#include "bsgs.h"
 #include "ctx.h"
 #include "field.h"
 #include "segdecode.h"
 #include "segments.h"
-#include "senderlog.h"
 
 namespace qk {
 
@@ -87,23 +86,8 @@ __global__ __launch_bounds__(SD_BLOCK) void k_snd_find(const uint32_t *__restric
 }
 
 // ----------------------------------------------------------------- prefix
-// lane j of a G-group: start = x^(j+1), step = x^G (canonical), as the
-// segmented encode's groups (segments.hip sg_group_powers)
-template <int G>
-__device__ __forceinline__ void sn_group_powers(uint32_t x, int j, uint32_t &start, uint32_t &step) {
-    uint32_t b = x, r = 1;
-    const uint32_t e = (uint32_t)j + 1;
-#pragma unroll
-    for (int bit = 0; (1 << bit) <= G; ++bit) {
-        const uint32_t rb = mul32_lazy(r, b);
-        r = ((e >> bit) & 1) ? rb : r;
-        if ((1 << bit) < G) b = mul32_lazy(b, b);
-    }
-    start = r;
-    step = canon32(b);
-}
-
-// G lanes per id, lane j a chain of K powers j+1, j+1+G, ... (G * K >= T).
+// G lanes per id, lane j a chain of K powers j+1, j+1+G, ... (G * K >= T;
+// field.h group_chain32, as the segmented encode's groups).
 // An item of fewer than SN_WAVES segments (a slice of a long one among them)
 // is walked by all waves, striped; otherwise wave w takes segments w, w +
 // SN_WAVES, ...: either way a wave adds up its own entries of ONE segment in
@@ -141,28 +125,13 @@ __global__ __launch_bounds__(SD_BLOCK) void k_snd_prefix(const uint32_t *__restr
         uint64_t acc[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) acc[k] = 0;
-        for (uint32_t i = b + first; i < e; i += stride) {
-            const uint32_t x = canon32(log[it.lo + i]);
-            uint32_t start, step;
-            if constexpr (G == 1) { start = x; step = x; }
-            else sn_group_powers<G>(x, j, start, step);
-            const uint32_t step5 = times5_32(step);
-            uint64_t t = start;
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                acc[k] += t;   // t < 6 * 2^32, at most SD_ITEM terms
-                if (k + 1 < K) t = tstep32p(t, step, step5, 0u);
-            }
-        }
+        // terms < 6 * 2^32, at most SD_ITEM of them
+        for (uint32_t i = b + first; i < e; i += stride) group_chain32<G, K>(acc, canon32(log[it.lo + i]), j);
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             uint64_t v = fold64_32(acc[k]);
 #pragma unroll
-            for (int off = 32; off >= G; off >>= 1) {
-                const uint32_t lo = __shfl_xor((int)(uint32_t)v, off, 64);
-                const uint32_t hi = __shfl_xor((int)(uint32_t)(v >> 32), off, 64);
-                v += ((uint64_t)hi << 32) | lo;   // < 2^38
-            }
+            for (int off = 32; off >= G; off >>= 1) v += bsgs::shfl_xor_u64(v, off);   // < 2^38
             const uint32_t m = lane + (uint32_t)k * G;
             if (lane < G && m < T && v) atomicAdd(&acc_out[g * T + m], (unsigned long long)v);
         }
@@ -284,19 +253,6 @@ __global__ __launch_bounds__(SD_BLOCK) void k_snd_finish(const uint32_t *__restr
     for (uint32_t k = j; k < T; k += SN_GROUP) mo[4 + k] = canon32(fold64_32(acc[g * T + k]));
 }
 
-// ------------------------------------------------------------------ drain
-// DR_ITEM, DrItem and dr_copy: senderlog.h (the log update moves its kept entries the same way)
-__global__ __launch_bounds__(SD_BLOCK) void k_log_drain(const DrItem *__restrict__ items, uint32_t nitems,
-                                                        const uint32_t *__restrict__ log,
-                                                        const uint32_t *__restrict__ aux, uint32_t *__restrict__ out,
-                                                        uint32_t *__restrict__ aux_out) {
-    const uint32_t w = blockIdx.x * SN_WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (w >= nitems) return;
-    const DrItem it = items[w];
-    dr_copy(log + it.src, out + it.dst, it.n, lane);
-    if (aux) dr_copy(aux + it.src, aux_out + it.dst, it.n, lane);
-}
-
 // ------------------------------------------------------------------- host
 // the step's own per-segment buffers, beside the decode's in the per-flow arena
 struct SnSeg {
@@ -334,13 +290,6 @@ static void sn_prefix(const uint32_t *log, const SdPlan &p, uint32_t T, const Sn
     else sn_prefix_gk<32, 32>(log, p, T, b, s);
 }
 
-static bool sn_overlap(const void *p, size_t pn, const void *q, size_t qn) {
-    if (!p || !q || !pn || !qn) return false;
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + qn && b < a + pn;
-}
-static bool sn_dev(const void *p) { return p && ((uintptr_t)p & 3) == 0 && is_device_ptr(p); }
-
 } // namespace qk
 
 using namespace qk;
@@ -351,7 +300,7 @@ extern "C" int qk_u32_sender_step_segments_device(qk_ctx *ctx, const uint8_t *d_
                                                   uint8_t *d_mine_out, uint8_t *action, uint64_t *drain,
                                                   uint64_t *hits, size_t cap, uint64_t *hit_offsets, size_t *n_hits,
                                                   void *stream) {
-    if (int e = sd_check(ctx, threshold)) return e;
+    if (int e = check_ctx_threshold(ctx, threshold)) return e;
     if (n_hits) *n_hits = 0;
     if (nseg == 0) {
         if (hit_offsets) hit_offsets[0] = 0;
@@ -364,14 +313,14 @@ extern "C" int qk_u32_sender_step_segments_device(qk_ctx *ctx, const uint8_t *d_
     const uint32_t T = threshold;
     const size_t rec = qk_u32_size(T);
     const uint64_t n = offsets[nseg] - offsets[0];
-    if (!sn_dev(d_mine) || !sn_dev(d_peer) || !sn_dev(d_mine_out) || (d_present && !is_device_ptr(d_present)) ||
-        (n && !sn_dev(d_log)))
+    if (!dev_words(d_mine) || !dev_words(d_peer) || !dev_words(d_mine_out) || (d_present && !is_device_ptr(d_present)) ||
+        (n && !dev_words(d_log)))
         return QK_E_INVAL;
     if (is_device_ptr(action) || is_device_ptr(drain) || is_device_ptr(hit_offsets) || (cap && is_device_ptr(hits)))
         return QK_E_INVAL;
-    if (sn_overlap(d_mine_out, nseg * rec, d_mine, nseg * rec) || sn_overlap(d_mine_out, nseg * rec, d_peer, nseg * rec) ||
-        sn_overlap(d_mine_out, nseg * rec, d_present, nseg) ||
-        sn_overlap(d_mine_out, nseg * rec, n ? d_log + offsets[0] : nullptr, n * 4))
+    if (ranges_overlap(d_mine_out, nseg * rec, d_mine, nseg * rec) || ranges_overlap(d_mine_out, nseg * rec, d_peer, nseg * rec) ||
+        ranges_overlap(d_mine_out, nseg * rec, d_present, nseg) ||
+        ranges_overlap(d_mine_out, nseg * rec, n ? d_log + offsets[0] : nullptr, n * 4))
         return QK_E_INVAL;
     std::lock_guard<std::mutex> lk(ctx->mu);
     QK_HIP_TRY(hipSetDevice(ctx->device));
@@ -438,50 +387,4 @@ extern "C" int qk_u32_sender_step_segments_device(qk_ctx *ctx, const uint8_t *d_
     if (rc) return rc;
     if (err) return QK_E_MISMATCH;
     return sd_collect(p, status.data(), segcnt.data(), total, nseg, hits, cap, hit_offsets, n_hits);
-}
-
-extern "C" int qk_u32_log_drain_segments_device(qk_ctx *ctx, const uint32_t *d_log, const uint32_t *d_aux,
-                                                const uint64_t *offsets, const uint64_t *drain, size_t nseg,
-                                                uint32_t *d_log_out, uint32_t *d_aux_out, size_t cap,
-                                                uint64_t *offsets_out, void *stream) {
-    if (!ctx) return QK_E_INVAL;
-    if (nseg == 0) {
-        if (offsets_out) offsets_out[0] = 0;
-        return QK_OK;
-    }
-    if (!offsets || !drain || !offsets_out || (d_aux == nullptr) != (d_aux_out == nullptr)) return QK_E_INVAL;
-    for (size_t g = 0; g < nseg; ++g)
-        if (offsets[g + 1] < offsets[g] || drain[g] > offsets[g + 1] - offsets[g]) return QK_E_INVAL;
-    offsets_out[0] = 0;
-    for (size_t g = 0; g < nseg; ++g) offsets_out[g + 1] = offsets_out[g] + (offsets[g + 1] - offsets[g] - drain[g]);
-    const uint64_t left = offsets_out[nseg], n = offsets[nseg] - offsets[0];
-    if (left > cap) return QK_E_CAPACITY;
-    if (left == 0) return QK_OK;
-    if (!sn_dev(d_log) || !sn_dev(d_log_out) || (d_aux && (!sn_dev(d_aux) || !sn_dev(d_aux_out)))) return QK_E_INVAL;
-    const void *in[2] = {d_log + offsets[0], d_aux ? d_aux + offsets[0] : nullptr};
-    const void *out[2] = {d_log_out, d_aux_out};
-    for (int o = 0; o < 2; ++o)
-        for (int i = 0; i < 2; ++i)
-            if (sn_overlap(out[o], left * 4, in[i], n * 4)) return QK_E_INVAL;
-    if (sn_overlap(d_log_out, left * 4, d_aux_out, left * 4)) return QK_E_INVAL;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    QK_HIP_TRY(hipSetDevice(ctx->device));
-    hipStream_t s = pick_stream(ctx, stream);
-    size_t ni = 0;
-    for (size_t g = 0; g < nseg; ++g) ni += (size_t)((offsets_out[g + 1] - offsets_out[g] + DR_ITEM - 1) / DR_ITEM);
-    if (ni > 0xFFFFFFFFull) return QK_E_INVAL;
-    if (int e = ensure_items(ctx, ni * sizeof(DrItem))) return e;
-    DrItem *items = (DrItem *)ctx->h_items;
-    size_t k = 0;
-    for (size_t g = 0; g < nseg; ++g) {
-        const uint64_t len = offsets_out[g + 1] - offsets_out[g], src = offsets[g] + drain[g];
-        for (uint64_t o = 0; o < len; o += DR_ITEM)
-            items[k++] = {src + o, offsets_out[g] + o, (uint32_t)std::min<uint64_t>(DR_ITEM, len - o), 0u};
-    }
-    hipLaunchKernelGGL(k_log_drain, dim3((uint32_t)((ni + SN_WAVES - 1) / SN_WAVES)), dim3(SD_BLOCK), 0, s,
-                       (const DrItem *)ctx->h_items_dev, (uint32_t)ni, d_log, d_aux, d_log_out, d_aux_out);
-    int rc = hipGetLastError() == hipSuccess ? QK_OK : QK_E_HIP;
-    // the pinned items must outlive the kernel
-    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = QK_E_HIP;
-    return rc;
 }

@@ -22,13 +22,16 @@
 //                   output array is written
 //   (host)          counts from the starts; offsets_out and the copy items
 //                   from offsets, drain and counts (senderlog.h)
-//   k_log_update    a wave per item: kept entries as k_log_drain moves them
+//   k_log_update    a wave per item: kept entries by a straight copy
 //                   (dr_copy), a flow's new entries as a gather through the
 //                   permutation, out[dst + j] = new_ids[perm[src + j]] — the
 //                   stores consecutive, only the batch's loads indirect (with
 //                   aux: one 8-byte load of the (id, aux) pair k_sl_count laid
 //                   side by side)
 // No workgroup waits on another inside a kernel: kernel boundaries order them.
+//
+// The drain alone (qk_u32_log_drain_segments_device, at the end) is the same
+// plan with an empty batch and the same kernel, with no sort and no wait.
 #include <algorithm>
 
 #include "ctx.h"
@@ -115,64 +118,19 @@ __global__ __launch_bounds__(SL_BLOCK) void k_log_update(const DrItem *__restric
 }
 
 // ------------------------------------------------------------------- host
-static int sl_bit_width(uint32_t v) { return v ? 32 - __builtin_clz(v) : 0; }
-
 // the sort's buffers in the per-packet arena: X and Y each hold n_new (key,
 // value) pairs, as two arrays (values after keys) or as one pair array
 struct SlSort {
-    uint32_t *x = nullptr, *y = nullptr, *cnt = nullptr, *base = nullptr, *tot = nullptr;
-    uint8_t *dig = nullptr;
+    uint32_t *x = nullptr, *y = nullptr;
+    RsScratch sc{};
     uint2 *pairs = nullptr;   // aux mode: (id, aux) per entry for the gather
 };
 static void sl_carve(Carve &cv, SlSort &b, uint64_t n, uint32_t nwg, bool pairs) {
     if (pairs) b.pairs = cv.take<uint2>(n);
     b.x = cv.take<uint32_t>(2 * n);
     b.y = cv.take<uint32_t>(2 * n);
-    b.cnt = cv.take<uint32_t>((size_t)rsort::R * nwg);
-    b.base = cv.take<uint32_t>((size_t)rsort::R * nwg);
-    b.tot = cv.take<uint32_t>(rsort::R);
-    b.dig = cv.take<uint8_t>(n + 16);
+    b.sc.take(cv, nwg, n);
 }
-
-// Stable sort of (flow[i], i) by the low `bits` bits of the flow index; the
-// first pass's counts are in b.cnt (k_sl_count) and the values in b.x + n.
-// flows.hip rs_sort_k's sequence with the caller's key array read by the first
-// pass only (it is never a pair array's place).  Returns the sorted keys and
-// the permutation.
-static int sl_sort(const uint32_t *flow, uint64_t n, int bits, uint32_t nwg, uint64_t chunk, const SlSort &b,
-                   hipStream_t s, const uint32_t **keys, const uint32_t **perm) {
-    constexpr int D = rsort::DBITS, BLK = 256, K = 16;
-    const int passes = (bits + D - 1) / D;
-    const int dd = (bits + passes - 1) / passes;   // balanced digits
-    for (int q = 0; q < passes; ++q) {
-        const uint32_t shift = (uint32_t)(q * dd);
-        const int left = bits - q * dd;
-        const uint32_t mask = left >= dd ? (1u << dd) - 1 : (1u << left) - 1;
-        const bool ip = q > 0, op = q + 1 < passes;
-        uint32_t *in = q % 2 ? b.y : b.x, *out = q % 2 ? b.x : b.y;
-        if (q > 0) hipLaunchKernelGGL(rsort::k_rs_count8, dim3(nwg), dim3(256), 0, s, b.dig, n, chunk, nwg, b.cnt);
-        hipLaunchKernelGGL(rsort::k_row_scan<256>, dim3(1u << D), dim3(256), 0, s, b.cnt, nwg, b.base, b.tot);
-        auto kern = ip ? (op ? rsort::k_rs_scatter<D, BLK, K, true, true> : rsort::k_rs_scatter<D, BLK, K, true, false>)
-                       : (op ? rsort::k_rs_scatter<D, BLK, K, false, true> : rsort::k_rs_scatter<D, BLK, K, false, false>);
-        const uint32_t nshift = (uint32_t)((q + 1) * dd);
-        const int nleft = bits - (q + 1) * dd;
-        const uint32_t nmask = nleft >= dd ? (1u << dd) - 1 : (1u << (nleft > 0 ? nleft : 0)) - 1;
-        hipLaunchKernelGGL(kern, dim3(nwg), dim3(BLK), 0, s, q ? (const uint32_t *)in : flow,
-                           (const uint32_t *)(in + n), n, chunk, shift, mask, nwg, (const uint32_t *)b.base,
-                           (const uint32_t *)b.tot, out, out + n, op ? b.dig : (uint8_t *)nullptr, nshift, nmask);
-        if (hipGetLastError() != hipSuccess) return QK_E_HIP;
-    }
-    *keys = passes % 2 ? b.y : b.x;
-    *perm = *keys + n;
-    return QK_OK;
-}
-
-static bool sl_overlap(const void *p, size_t pn, const void *q, size_t qn) {
-    if (!p || !q || !pn || !qn) return false;
-    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-    return a < b + qn && b < a + pn;
-}
-static bool sl_dev(const void *p) { return p && ((uintptr_t)p & 3) == 0 && is_device_ptr(p); }
 
 } // namespace qk
 
@@ -199,18 +157,18 @@ extern "C" int qk_u32_log_update_segments_device(qk_ctx *ctx, const uint32_t *d_
     std::lock_guard<std::mutex> lk(ctx->mu);
     QK_HIP_TRY(hipSetDevice(ctx->device));
     if (is_device_ptr(offsets) || is_device_ptr(offsets_out) || (drain && is_device_ptr(drain))) return QK_E_INVAL;
-    if (n_in && (!sl_dev(d_log) || (auxm && !sl_dev(d_aux)))) return QK_E_INVAL;
-    if (n_new && (!sl_dev(d_new_flow) || !sl_dev(d_new_ids) || (auxm && !sl_dev(d_new_aux)))) return QK_E_INVAL;
+    if (n_in && (!dev_words(d_log) || (auxm && !dev_words(d_aux)))) return QK_E_INVAL;
+    if (n_new && (!dev_words(d_new_flow) || !dev_words(d_new_ids) || (auxm && !dev_words(d_new_aux)))) return QK_E_INVAL;
     const uint64_t wr = std::min<uint64_t>(cap, total);   // what a call of this cap can write
-    if (wr && (!sl_dev(d_log_out) || (auxm && !sl_dev(d_aux_out)))) return QK_E_INVAL;
+    if (wr && (!dev_words(d_log_out) || (auxm && !dev_words(d_aux_out)))) return QK_E_INVAL;
     const void *in[5] = {n_in ? d_log + offsets[0] : nullptr, n_in && d_aux ? d_aux + offsets[0] : nullptr, d_new_flow,
                          d_new_ids, d_new_aux};
     const size_t inb[5] = {(size_t)n_in * 4, (size_t)n_in * 4, n_new * 4, n_new * 4, n_new * 4};
     const void *out[2] = {d_log_out, d_aux_out};
     for (int o = 0; o < 2; ++o)
         for (int i = 0; i < 5; ++i)
-            if (sl_overlap(out[o], (size_t)wr * 4, in[i], inb[i])) return QK_E_INVAL;
-    if (sl_overlap(d_log_out, (size_t)wr * 4, d_aux_out, (size_t)wr * 4)) return QK_E_INVAL;
+            if (ranges_overlap(out[o], (size_t)wr * 4, in[i], inb[i])) return QK_E_INVAL;
+    if (ranges_overlap(d_log_out, (size_t)wr * 4, d_aux_out, (size_t)wr * 4)) return QK_E_INVAL;
     hipStream_t s = pick_stream(ctx, stream);
 
     // pinned: the counts and the flag, then the items (their number bounded
@@ -227,11 +185,11 @@ extern "C" int qk_u32_log_update_segments_device(qk_ctx *ctx, const uint32_t *d_
     const uint2 *pairs = nullptr;
     int rc = QK_OK;
     if (n_new) {
-        const int bits = sl_bit_width((uint32_t)(nseg - 1));
-        const uint32_t nwg = (uint32_t)std::max<uint64_t>(
-            1, std::min<uint64_t>((uint64_t)ctx->num_cus * SL_WGPC, ((uint64_t)n_new + 4095) / 4096));
-        // 16-item chunks: k_rs_count8's loads of the digit bytes
-        const uint64_t chunk = ((((uint64_t)n_new + nwg - 1) / nwg) + 15) & ~(uint64_t)15;
+        const int bits = bit_width32((uint32_t)(nseg - 1));
+        // 16-item chunks: k_rs_count8's loads of the digit bytes (rs_sort_k rounds its plan the same way)
+        RsPlan pl = rs_plan(ctx, n_new, SL_WGPC);
+        pl.chunk = (pl.chunk + 15) & ~(uint64_t)15;
+        const uint32_t nwg = pl.nwg;
         SlSort b;
         uint32_t *fcnt = nullptr;
         for (int pass = 0; pass < 2; ++pass) {
@@ -245,18 +203,22 @@ extern "C" int qk_u32_log_update_segments_device(qk_ctx *ctx, const uint32_t *d_
         }
         const int passes = (bits + rsort::DBITS - 1) / rsort::DBITS;
         const uint32_t mask0 = passes ? (1u << ((bits + passes - 1) / passes)) - 1 : 0u;
-        const uint32_t *keys = nullptr;
         // fcnt: every start and the flag ~0
         if (hipMemsetAsync(fcnt, 0xFF, (nseg + 1) * sizeof(uint32_t), s) != hipSuccess) rc = QK_E_HIP;
         if (!rc) {
-            hipLaunchKernelGGL(k_sl_count, dim3(nwg), dim3(SL_BLOCK), 0, s, d_new_flow, (uint64_t)n_new, chunk,
+            hipLaunchKernelGGL(k_sl_count, dim3(nwg), dim3(SL_BLOCK), 0, s, d_new_flow, (uint64_t)n_new, pl.chunk,
                                (uint32_t)nseg, mask0, nwg, fcnt + nseg, b.x + n_new,
-                               passes ? b.cnt : (uint32_t *)nullptr, d_new_ids, d_new_aux, b.pairs);
+                               passes ? b.sc.cnt : (uint32_t *)nullptr, d_new_ids, d_new_aux, b.pairs);
             if (hipGetLastError() != hipSuccess) rc = QK_E_HIP;
         }
         pairs = b.pairs;
-        if (!rc && passes) rc = sl_sort(d_new_flow, n_new, bits, nwg, chunk, b, s, &keys, &perm);
+        // the first pass reads d_new_flow in place (its counts: k_sl_count's); X and Y are the sort's own
+        int where = 0;
+        if (!rc && passes)
+            rc = rs_sort(ctx, b.x, b.x + n_new, b.y, b.y + n_new, n_new, bits, b.sc, s, where, &pl, true, d_new_flow);
         if (!rc && passes) {
+            const uint32_t *keys = where ? b.y : b.x;
+            perm = keys + n_new;
             hipLaunchKernelGGL(k_sl_starts, dim3(nwg), dim3(SL_BLOCK), 0, s, keys, (uint32_t)n_new, (uint32_t)nseg, fcnt);
             if (hipGetLastError() != hipSuccess) rc = QK_E_HIP;
         }
@@ -284,5 +246,64 @@ extern "C" int qk_u32_log_update_segments_device(qk_ctx *ctx, const uint32_t *d_
     }
     // the pinned items and the arenas must outlive what was enqueued (the sort too, when the call fails)
     if ((n_new || ni) && hipStreamSynchronize(s) != hipSuccess && !rc) rc = QK_E_HIP;
+    return rc;
+}
+
+// The drain once offsets and drain are known to be valid (left entries stay,
+// in ni copy items): capacity, then the pointers, then the copy.  *planned:
+// offsets_out was written together with the items (one pass over the flows,
+// as the update plans; 10^5 flows: a pass costs a tenth of the call).
+static int sl_drain_copy(qk_ctx *ctx, const uint32_t *d_log, const uint32_t *d_aux, const uint64_t *offsets,
+                         const uint64_t *drain, size_t nseg, uint32_t *d_log_out, uint32_t *d_aux_out, size_t cap,
+                         uint64_t *offsets_out, void *stream, uint64_t left, size_t ni, bool *planned) {
+    const uint64_t n = offsets[nseg] - offsets[0];
+    if (left > cap) return QK_E_CAPACITY;
+    if (left == 0) return QK_OK;
+    if (!dev_words(d_log) || !dev_words(d_log_out) || (d_aux && (!dev_words(d_aux) || !dev_words(d_aux_out))))
+        return QK_E_INVAL;
+    const void *in[2] = {d_log + offsets[0], d_aux ? d_aux + offsets[0] : nullptr};
+    const void *out[2] = {d_log_out, d_aux_out};
+    for (int o = 0; o < 2; ++o)
+        for (int i = 0; i < 2; ++i)
+            if (ranges_overlap(out[o], left * 4, in[i], n * 4)) return QK_E_INVAL;
+    if (ranges_overlap(d_log_out, left * 4, d_aux_out, left * 4)) return QK_E_INVAL;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    QK_HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = pick_stream(ctx, stream);
+    if (ni > 0xFFFFFFFFull) return QK_E_INVAL;
+    if (int e = ensure_items(ctx, ni * sizeof(DrItem))) return e;
+    sl_plan(offsets, drain, nullptr, nseg, offsets_out, (DrItem *)ctx->h_items);
+    *planned = true;
+    hipLaunchKernelGGL(k_log_update, dim3((uint32_t)((ni + SL_WAVES - 1) / SL_WAVES)), dim3(SL_BLOCK), 0, s,
+                       (const DrItem *)ctx->h_items_dev, (uint32_t)ni, d_log, d_aux, (const uint32_t *)nullptr,
+                       (const uint32_t *)nullptr, (const uint2 *)nullptr, (const uint32_t *)nullptr, d_log_out, d_aux_out);
+    int rc = hipGetLastError() == hipSuccess ? QK_OK : QK_E_HIP;
+    // the pinned items must outlive the kernel
+    if (hipStreamSynchronize(s) != hipSuccess && !rc) rc = QK_E_HIP;
+    return rc;
+}
+
+// seqno_ids.drain(..idx+1) for all flows without new entries: the update's
+// plan with an empty batch (counts == nullptr: kept items only) and its copy
+// kernel, behind the drain's own argument rules (drain required, aux and
+// aux_out together, capacity decided before any pointer is classified).
+extern "C" int qk_u32_log_drain_segments_device(qk_ctx *ctx, const uint32_t *d_log, const uint32_t *d_aux,
+                                                const uint64_t *offsets, const uint64_t *drain, size_t nseg,
+                                                uint32_t *d_log_out, uint32_t *d_aux_out, size_t cap,
+                                                uint64_t *offsets_out, void *stream) {
+    if (!ctx) return QK_E_INVAL;
+    if (nseg == 0) {
+        if (offsets_out) offsets_out[0] = 0;
+        return QK_OK;
+    }
+    if (!offsets || !drain || !offsets_out || (d_aux == nullptr) != (d_aux_out == nullptr)) return QK_E_INVAL;
+    uint64_t left = 0;
+    size_t ni = 0;
+    if (!sl_check(offsets, drain, nseg, &left, &ni)) return QK_E_INVAL;
+    bool planned = false;
+    const int rc = sl_drain_copy(ctx, d_log, d_aux, offsets, drain, nseg, d_log_out, d_aux_out, cap, offsets_out, stream,
+                                 left, ni, &planned);
+    // valid offsets and drain: offsets_out is written whatever else the call returns
+    if (!planned) sl_plan(offsets, drain, nullptr, nseg, offsets_out, nullptr);
     return rc;
 }

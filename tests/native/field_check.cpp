@@ -75,6 +75,39 @@ static void check_mulfold(uint32_t y, uint32_t x) {
     if (m >= 25) EXPECT(m == e, "min form != exact with r >= 25 y=%u x=%u", y, x);
 }
 
+// group_powers32 / group_chain32 (the power chains of the G > 1 encode, the
+// segmented encode and the sender step's prefix): lane j of a G-group starts
+// at x^(j+1) and steps by x^G.  x is any 32-bit value: mul32_lazy takes lazy
+// operands (y, x < 2^32), so the raw ids the G > 1 encode passes are in range.
+template <int G>
+static void check_group(uint32_t x) {
+    const uint32_t xc = canon32(x);
+    for (int j = 0; j < G; ++j) {
+        uint32_t start = 0xDEADBEEFu, step = 0xDEADBEEFu;
+        group_powers32<G>(x, j, start, step);
+        EXPECT(canon32(start) == pow32(xc, (uint64_t)j + 1), "group_powers32<%d> start x=%u j=%d", G, x, j);
+        EXPECT(step == pow32(xc, G), "group_powers32<%d> step x=%u j=%d -> %u", G, x, j, step);
+        // the chain on top of it, from the canonical id as the callers pass it
+        constexpr int K = 4;
+        uint64_t acc[K] = {1, 2, 3, 4};
+        group_chain32<G, K>(acc, xc, j);
+        for (int k = 0; k < K; ++k)
+            EXPECT((acc[k] - (uint64_t)(k + 1)) % P32 == pow32(xc, (uint64_t)j + 1 + (uint64_t)k * G),
+                   "group_chain32<%d> x=%u j=%d k=%d", G, x, j, k);
+    }
+}
+static void check_groups(uint32_t x) {
+    check_group<2>(x);
+    check_group<4>(x);
+    check_group<8>(x);
+    check_group<16>(x);
+    check_group<32>(x);
+    // one lane per id: the chain from the id itself
+    uint64_t acc[3] = {0, 0, 0};
+    group_chain32<1, 3>(acc, canon32(x), 0);
+    for (int k = 0; k < 3; ++k) EXPECT(acc[k] % P32 == pow32(canon32(x), (uint64_t)k + 1), "group_chain32<1> x=%u k=%d", x, k);
+}
+
 static int run_check() {
     const uint32_t edges32[] = {0, 1, 2, 3, 4, 5, 6, P32 - 2, P32 - 1, P32, P32 + 1, P32 + 4, 0xFFFFFFFFu,
                                 0x80000000u, 0x7FFFFFFFu, 0xFFFFFFF0u};
@@ -91,6 +124,9 @@ static int run_check() {
         for (uint32_t x : edges32) check_mulfold(y, x);
     for (int i = 0; i < 2000000; ++i) check_mulfold(r32(), r32());
     for (uint32_t x : edges32) EXPECT(canon32(x) == x % P32, "canon32 %u", x);
+    for (uint32_t x : {0u, 1u, 2u, P32 - 1, P32, P32 + 1, 0xFFFFFFFFu}) check_groups(x);
+    for (uint32_t x : edges32) check_groups(x);
+    for (int i = 0; i < 500; ++i) check_groups(r32());
     // 64-bit accumulator folds
     const uint64_t a64[] = {0, 1, ~0ull, ~0ull - 1, 1ull << 63, (1ull << 32) - 1, 1ull << 32, P32, 25ull << 32};
     for (uint64_t a : a64) EXPECT(canon32(fold64_32(a)) == a % P32, "fold64_32 %llu", (unsigned long long)a);

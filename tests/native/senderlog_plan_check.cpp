@@ -7,6 +7,8 @@
 // model's offsets, and for every output position exactly one item must cover
 // it, of the right kind and with the right source; no item is empty or longer
 // than DR_ITEM, and sl_items_bound is no less than the item count.
+// Then the entry points' overlap test (argcheck.h ranges_overlap) on byte
+// ranges of one buffer.
 //
 //   senderlog_plan_check          edge shapes, then 300 random shapes
 #include <stdint.h>
@@ -15,6 +17,7 @@
 #include <random>
 #include <vector>
 
+#include "../../sidekick_amd/csrc/argcheck.h"
 #include "../../sidekick_amd/csrc/senderlog.h"
 
 using namespace qk;
@@ -135,6 +138,19 @@ int main() {
         if (sl_counts_from_starts(b, 3, 9)) fail("starts that leave out position 0 accepted", shape, 0);
         if (sl_counts_from_starts(c, 3, 9)) fail("a start at the batch's end accepted", shape, 0);
         if (sl_counts_from_starts(d, 2, 4)) fail("no start for a batch with entries accepted", shape, 0);
+    }
+    {
+        const char buf[64] = {0};
+        const char *p = buf;
+        if (ranges_overlap(p, 16, p + 32, 16)) fail("disjoint ranges overlap", shape, 0);
+        if (ranges_overlap(p, 16, p + 16, 16) || ranges_overlap(p + 16, 16, p, 16))
+            fail("touching ranges overlap", shape, 0);
+        if (!ranges_overlap(p, 17, p + 16, 16) || !ranges_overlap(p + 16, 16, p, 17))
+            fail("ranges sharing one byte do not overlap", shape, 0);
+        if (!ranges_overlap(p, 64, p + 8, 4) || !ranges_overlap(p + 8, 4, p, 64)) fail("nested ranges do not overlap", shape, 0);
+        if (!ranges_overlap(p, 8, p, 8)) fail("equal ranges do not overlap", shape, 0);
+        if (ranges_overlap(nullptr, 8, p, 8) || ranges_overlap(p, 8, nullptr, 8)) fail("a null range overlaps", shape, 0);
+        if (ranges_overlap(p + 4, 0, p, 8) || ranges_overlap(p, 8, p + 4, 0)) fail("an empty range overlaps", shape, 0);
     }
     std::mt19937_64 rng(0x5E4DE7106ull);
     for (int r = 0; r < 300; ++r) {
