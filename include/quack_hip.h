@@ -517,6 +517,69 @@ int qk_u32_flows_lookup_device(qk_ctx *ctx, const qk_flow_key *d_keys, const uin
                                uint8_t *found, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Device wire leg: the message between the proxy's flow table and the sender's
+ * step, built and parsed where the records live.  The image is the one of
+ * qk_u32_serialize / qk_u32_deserialize: u64 threshold, threshold u32 power
+ * sums, the u8 Option tag of last_value, last_value (u32, only when the tag
+ * is 1), u32 count; little-endian, nothing aligned; 4 * threshold + 13 or + 17
+ * bytes.  Both calls are synchronous on `stream`.
+ * NULL ctx -> QK_E_INVAL before any other check; threshold 0 or > 1024 ->
+ * QK_E_THRESHOLD; a host pointer where a device one is required or the
+ * reverse, n (or nseg) >= 2^32, an output range overlapping an input range or
+ * another output -> QK_E_INVAL.  Records, keys, rows, lengths and flow indices
+ * are 4-byte aligned; the image buffers may have any byte alignment.
+ * ---------------------------------------------------------------------- */
+/* the longest image of a threshold: 4 * threshold + 17 */
+size_t qk_u32_wire_max(uint32_t threshold);
+
+/* status of a well-formed image that a later one for the same flow replaced */
+#define QK_WIRE_SUPERSEDED 1
+
+/* bincode::serialize(&quack) per due flow (sidekick_multi.rs:274-283) for the
+ * selected flows of a flow array (d_keys, d_sk: n records of
+ * qk_u32_size(threshold) bytes).  d_select: n device bytes, non-zero = emit
+ * the flow (what qk_u32_flows_merge_device writes as due_out); NULL = every
+ * flow.  The m selected flows come out in array order: image r at d_wire_out +
+ * r * stride, byte-equal to qk_u32_serialize of the record (4 bytes shorter
+ * when has_last == 0), its length in d_len_out[r], its key in d_keys_out[r]
+ * (may be NULL; d_keys may then be NULL too), its row index in the input in
+ * d_rows_out[r] (may be NULL).  stride >= qk_u32_wire_max(threshold) and
+ * < 2^32, odd values included, else QK_E_INVAL.  Bytes of a slot past its length are
+ * unspecified; nothing is written outside the m * stride bytes of the slots.
+ * *n_out = m; cap < m -> QK_E_CAPACITY with *n_out set and no output array
+ * written.  A selected record whose threshold field differs from `threshold`
+ * (found on the device) -> QK_E_MISMATCH, the outputs unspecified. */
+int qk_u32_flows_emit_device(qk_ctx *ctx, const qk_flow_key *d_keys, const uint8_t *d_sk, size_t n,
+                             uint32_t threshold, const uint8_t *d_select, size_t stride,
+                             qk_flow_key *d_keys_out, uint32_t *d_rows_out, uint8_t *d_wire_out,
+                             uint32_t *d_len_out, size_t cap, size_t *n_out, void *stream);
+
+/* bincode::deserialize(&buf[..len]) per datagram (media_client.rs:226-227) for
+ * a batch of n received datagrams, placed by flow: datagram i lies at d_wire +
+ * i * stride, d_len[i] bytes long, and belongs to flow d_flow[i] (the caller
+ * knows it from the socket; the reference sends no key).  status[i] (host, n
+ * entries) is what qk_u32_deserialize returns for those bytes into a sketch of
+ * `threshold`: QK_OK, QK_E_FORMAT, or QK_E_MISMATCH for a well-formed image of
+ * another threshold; d_len[i] > stride -> QK_E_FORMAT.  No byte past
+ * min(d_len[i], stride) of a slot is read, whatever the image claims.
+ * Last wins — a rule of the batch (the reference handles one datagram per loop
+ * turn; quACKs are cumulative, so a sender that received several for a flow
+ * since its last step needs only the newest): among the accepted datagrams of
+ * flow g the one with the largest i goes to row g of d_peer (nseg records of
+ * qk_u32_size(threshold) bytes; the threshold field set to `threshold`) with
+ * d_present[g] = 1, and the flow's earlier accepted datagrams get status
+ * QK_WIRE_SUPERSEDED (a caller that wants every quACK stepped runs those in an
+ * earlier call).  A flow without an accepted datagram gets d_present[g] = 0
+ * and keeps its d_peer row.  *n_accepted = the winners.
+ * A d_flow[i] >= nseg (found on the device) -> QK_E_INVAL before d_peer or
+ * d_present is written.  n == 0 -> QK_OK with d_present all zero; nseg == 0
+ * with n > 0, or stride == 0 -> QK_E_INVAL. */
+int qk_u32_wire_ingest_device(qk_ctx *ctx, const uint8_t *d_wire, size_t stride, const uint32_t *d_len,
+                              const uint32_t *d_flow, size_t n, uint32_t threshold, size_t nseg,
+                              uint8_t *d_peer, uint8_t *d_present, int32_t *status, size_t *n_accepted,
+                              void *stream);
+
+/* ------------------------------------------------------------------------
  * Multi-GPU: the id stream cut into contiguous shards, one
  * per GPU in global rank order, merged with ONE RCCL reduce over xGMI.
  * The reference callers are single processes (sidekick.rs:58-127,

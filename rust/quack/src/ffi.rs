@@ -21,6 +21,8 @@ pub const QK_ID_OFFSET: usize = 63;
 pub const QK_BUFFER_SIZE: usize = 67;
 pub const QK_COMM_ID_BYTES: usize = 128;
 pub const QK_FLOW_JOIN_TILE: u32 = 2048;
+/// status of a well-formed image that a later one for the same flow replaced (qk_u32_wire_ingest_device)
+pub const QK_WIRE_SUPERSEDED: i32 = 1;
 // qk_u32_sender_step_segments_device's action per flow (the reset bits may be ORed)
 pub const QK_SND_IDLE: u8 = 0;
 pub const QK_SND_ADVANCED: u8 = 1;
@@ -255,6 +257,19 @@ extern "C" {
     pub fn qk_u32_flows_lookup_device(ctx: *mut qk_ctx, d_keys: *const qk_flow_key, d_sk: *const u8, n: usize,
                                       threshold: u32, keys: *const qk_flow_key, nk: usize, sketches: *mut u8,
                                       found: *mut u8, stream: *mut c_void) -> c_int;
+
+    // device wire leg: bincode::serialize per due flow (sidekick_multi.rs:274-283),
+    // bincode::deserialize per datagram (media_client.rs:226-227)
+    pub fn qk_u32_wire_max(threshold: u32) -> usize;
+    pub fn qk_u32_flows_emit_device(ctx: *mut qk_ctx, d_keys: *const qk_flow_key, d_sk: *const u8, n: usize,
+                                    threshold: u32, d_select: *const u8, stride: usize,
+                                    d_keys_out: *mut qk_flow_key, d_rows_out: *mut u32, d_wire_out: *mut u8,
+                                    d_len_out: *mut u32, cap: usize, n_out: *mut usize,
+                                    stream: *mut c_void) -> c_int;
+    pub fn qk_u32_wire_ingest_device(ctx: *mut qk_ctx, d_wire: *const u8, stride: usize, d_len: *const u32,
+                                     d_flow: *const u32, n: usize, threshold: u32, nseg: usize, d_peer: *mut u8,
+                                     d_present: *mut u8, status: *mut int32_t, n_accepted: *mut usize,
+                                     stream: *mut c_void) -> c_int;
 
     // multi-GPU over RCCL
     pub fn qk_comm_unique_id(id: *mut u8) -> c_int;

@@ -194,6 +194,7 @@ int warm_segdecode(hipStream_t s);
 int warm_sender(hipStream_t s);
 int warm_senderlog(hipStream_t s);
 int warm_flowtable(hipStream_t s);
+int warm_wire(hipStream_t s);
 int warm_comm(hipStream_t s);
 
 hipStream_t pick_stream(qk_ctx *ctx, void *stream);

@@ -53,6 +53,7 @@ __all__ = [
     "to_coeffs_segments", "decode_segments", "sender_step", "drain_segments", "SenderStep",
     "update_segments", "DeviceSenderLog", "SenderLogStep",
     "flows_merge", "flows_diff", "flows_lookup", "DeviceFlowQuacks",
+    "emit_wire", "ingest_wire", "wire_max",
 ]
 
 
@@ -856,6 +857,7 @@ class DeviceSenderLog:
         self.offsets = np.zeros(1, dtype=np.uint64)
         self.last_quack_reset = np.zeros(0, dtype=np.float64)
         self._pending = None                      # np.uint64 per flow: the drain not yet applied
+        self._peer = None                         # on_wire's record tensor: the last quACK received per flow
         self.add_flows(nflows)
 
     @property
@@ -930,6 +932,22 @@ class DeviceSenderLog:
                 retransmit[g] = vals[at:at + c]
                 at += c
         return SenderLogStep(action, fired, reason, retransmit)
+
+    def on_wire(self, wire, lens, flow, now: float = 0.0):
+        """A batch of received datagrams (ingest_wire: image i in row i of the
+        CUDA uint8 tensor `wire`, lens[i] bytes, of flow flow[i]) through
+        on_quacks: the newest accepted quACK of every flow is stepped, no
+        per-flow host work in between.  Returns (SenderLogStep, status), status
+        as ingest_wire gives it."""
+        import torch
+        nf = self.nflows
+        if self._peer is None or self._peer.shape[0] != nf:
+            old = self._peer
+            self._peer = self._fresh.unsqueeze(0).expand(nf, -1).contiguous()
+            if old is not None:
+                self._peer[:min(nf, old.shape[0])] = old[:nf]
+        _, present, status, _ = ingest_wire(wire, lens, flow, nf, self.threshold, peer=self._peer, ctx=self._ctx)
+        return self.on_quacks(self._peer, present=present, now=now), status
 
 
 def encode_flows(bufs, threshold: int, stride: int = 67, meta=None, my_addr=None, ctx: Context | None = None,
@@ -1152,6 +1170,98 @@ def flows_lookup(keys, sk, query, ctx: Context | None = None) -> list:
     return [_quack_from_bytes(raw[i * rec:(i + 1) * rec], t) if f[i] else None for i in range(nk)]
 
 
+def wire_max(threshold: int) -> int:
+    """The longest bincode image of a PowerSumQuackU32 of this threshold
+    (qk_u32_wire_max: 4 * threshold + 17 bytes)."""
+    return int(lib().qk_u32_wire_max(int(threshold)))
+
+
+def emit_wire(keys, sketches, select=None, stride: int | None = None, ctx: Context | None = None):
+    """bincode::serialize(&quack) for the selected flows of a flow array on the
+    device (qk_u32_flows_emit_device; the per-flow send of
+    sidekick_multi.rs:274-283).  `keys` / `sketches`: a flow array as
+    encode_flows(device_out=True) returns it (`keys` may be None: no keys come
+    back); `select`: a CUDA uint8/bool tensor of n flags, e.g. the `due` flags
+    of flows_merge, or None for every flow; `stride`: bytes between images
+    (default wire_max(t), the dense packing).  Returns (keys_out, rows, wire,
+    lens) as CUDA tensors, the m selected flows in array order: uint8 [m, 12]
+    (or None), int32 [m] row indices, uint8 [m, stride] images, int32 [m]
+    image lengths.  Image r is wire[r, :lens[r]], byte-equal to
+    sketches[rows[r]].serialize()."""
+    import torch
+    ctx = _flow_ctx(ctx, sketches, keys)
+    if keys is None:
+        ok = (isinstance(sketches, torch.Tensor) and sketches.is_cuda and sketches.dtype == torch.int32
+              and sketches.dim() == 2 and sketches.shape[1] > 4 and sketches.is_contiguous())
+        if not ok:
+            raise TypeError("sketches must be a contiguous CUDA int32 [n, 4 + t] record tensor")
+        n, t = sketches.shape[0], sketches.shape[1] - 4
+    else:
+        n, t = _flow_array(keys, sketches, "table")
+    stride = wire_max(t) if stride is None else int(stride)
+    if stride < wire_max(t):
+        raise QuackError(QK_E_INVAL, "emit_wire: stride below wire_max(threshold)")
+    if select is not None:
+        if not (isinstance(select, torch.Tensor) and select.is_cuda and select.dtype in (torch.uint8, torch.bool)
+                and select.is_contiguous() and select.numel() == n):
+            raise TypeError("select must be a contiguous CUDA uint8/bool tensor of one flag per flow")
+    device = sketches.device
+    keys_out = torch.empty((n, 12), dtype=torch.uint8, device=device) if keys is not None else None
+    rows = torch.empty((n,), dtype=torch.int32, device=device)
+    wire = torch.empty((n, stride), dtype=torch.uint8, device=device)
+    lens = torch.empty((n,), dtype=torch.int32, device=device)
+    m = C.c_size_t()
+    check(lib().qk_u32_flows_emit_device(
+        ctx.handle, keys.data_ptr() if keys is not None and n else None, sketches.data_ptr() if n else None, n, t,
+        select.data_ptr() if select is not None and n else None, stride,
+        keys_out.data_ptr() if keys_out is not None and n else None, rows.data_ptr() if n else None,
+        wire.data_ptr() if n else None, lens.data_ptr() if n else None, n, C.byref(m), _flow_stream(sketches)),
+        "emit_wire")
+    m = m.value
+    return (keys_out[:m] if keys_out is not None else None), rows[:m], wire[:m], lens[:m]
+
+
+def ingest_wire(wire, lens, flow, nflows: int, threshold: int, peer=None, ctx: Context | None = None):
+    """bincode::deserialize per received datagram (media_client.rs:226-227) for a
+    batch, placed by flow on the device (qk_u32_wire_ingest_device).  `wire`: a
+    contiguous CUDA uint8 tensor [n, stride], datagram i in row i; `lens` its
+    received lengths and `flow` its flow indices (CUDA int32 tensors, or host
+    arrays, uploaded).  Returns (peer, present, status, n_accepted): `peer` the
+    CUDA int32 record tensor [nflows, 4 + t] (the one passed in, else a fresh
+    one of empty quACKs) with the newest accepted image of every flow in its
+    row, `present` the CUDA uint8 flags of the flows that got one — both as
+    sender_step takes them — and `status` a host int32 array: QK_OK for a
+    winner, QK_WIRE_SUPERSEDED for an accepted image a later one of the same
+    flow replaced, else what deserialize returns for it."""
+    import torch
+    ctx = _flow_ctx(ctx, wire, peer)
+    nflows, t = int(nflows), int(threshold)
+    if not (isinstance(wire, torch.Tensor) and wire.is_cuda and wire.dtype == torch.uint8 and wire.dim() == 2
+            and wire.is_contiguous()):
+        raise TypeError("wire must be a contiguous CUDA uint8 tensor [n, stride]")
+    n, stride = wire.shape
+    device = wire.device
+    if _u32_len(lens, "lens") != n or _u32_len(flow, "flow") != n:
+        raise ValueError("lens and flow must hold one entry per datagram")
+    lens = _u32_on_device(lens, device, "lens")
+    flow = _u32_on_device(flow, device, "flow")
+    if peer is None:
+        fresh = torch.from_numpy(np.frombuffer(PowerSumQuackU32(t)._buf, dtype=np.int32).copy()).to(device)
+        peer = fresh.unsqueeze(0).expand(nflows, -1).contiguous()
+    elif not (isinstance(peer, torch.Tensor) and peer.is_cuda and peer.dtype == torch.int32 and peer.is_contiguous()
+              and tuple(peer.shape) == (nflows, 4 + t) and peer.device == device):
+        raise TypeError("peer must be a contiguous CUDA int32 record tensor [nflows, 4 + t] on wire's device")
+    present = torch.empty((nflows,), dtype=torch.uint8, device=device)
+    status = np.zeros(max(n, 1), dtype=np.int32)
+    acc = C.c_size_t()
+    check(lib().qk_u32_wire_ingest_device(
+        ctx.handle, wire.data_ptr() if n else None, max(int(stride), 1), lens.data_ptr() if n else None,
+        flow.data_ptr() if n else None, n, t, nflows, peer.data_ptr() if nflows else None,
+        present.data_ptr() if nflows else None, status.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(acc),
+        _flow_stream(wire)), "ingest_wire")
+    return peer, present, status[:n], acc.value
+
+
 class DeviceFlowQuacks:
     """SidekickMulti's flow table (sidekick_multi.rs:36,65-90) resident in HBM:
     FlowQuacks' surface over a key-sorted flow array.  A batch goes
@@ -1214,15 +1324,24 @@ class DeviceFlowQuacks:
         self._cur, self._n = o, n.value
         return do[:self._n]
 
+    def emit(self, select=None, stride: int | None = None, ctx: Context | None = None):
+        """The wire images of the selected flows of the table (emit_wire):
+        (keys, rows, wire, lens) as CUDA tensors; `select` None: every flow."""
+        ctx = ctx or get_context(self.device)
+        return emit_wire(self.keys, self.sketches, select, stride, ctx)
+
     def insert_packets(self, bufs, stride: int = 67, meta=None, my_addr=None, frequency_pkts: int = 0,
-                       ctx: Context | None = None) -> dict:
+                       ctx: Context | None = None, emit: bool = False) -> dict:
         """Batch of captured records (CUDA uint8 tensor): extract, group by
         AddrKey and encode per flow on the device, then merge into the table
         there.  A batch with a Reset replaces the table, as FlowQuacks does.
         stats["due"] lists the AddrKeys of the flows whose count crossed a
         multiple of frequency_pkts during the batch
         (start_sidekick_multi_frequency_pkts, sidekick_multi.rs:274); the quACK
-        to send for them is the end-of-batch one."""
+        to send for them is the end-of-batch one.  emit=True: the due flows'
+        wire images are built on the device instead, stats["wire"] = the
+        (keys, rows, wire, lens) of emit(select=due), and no key crosses to the
+        host (stats["due"] is then left empty)."""
         ctx = ctx or get_context(self.device)
         keys, sk, stats = encode_flows(bufs, self.threshold, stride, meta, my_addr, ctx, device_out=True,
                                        cap=self._batch_cap)
@@ -1232,7 +1351,9 @@ class DeviceFlowQuacks:
             self.clear()
         due = self.merge(keys, sk, frequency_pkts, ctx)
         stats["due"] = []
-        if frequency_pkts:
+        if emit:
+            stats["wire"] = self.emit(select=due, ctx=ctx)
+        elif frequency_pkts:
             hit = self.keys[due.bool()].cpu().numpy()
             stats["due"] = [hit[i].tobytes() for i in range(hit.shape[0])]
         return stats
