@@ -42,6 +42,7 @@ FLOW_JOIN_TILE = 2048   # QK_FLOW_JOIN_TILE: keys of a and b together per work i
 u8p = C.POINTER(C.c_uint8)
 u32p = C.POINTER(C.c_uint32)
 u64p = C.POINTER(C.c_uint64)
+i32p = C.POINTER(C.c_int32)
 vp = C.c_void_p
 vpp = C.POINTER(C.c_void_p)
 sz = C.c_size_t
@@ -170,10 +171,8 @@ def lib():
         # (libamdhip64.so.7), and the library must bind to that same copy —
         # loaded the other way round, torch finds the /opt/rocm runtime
         # already mapped under its soname and reports no GPU
-        try:
-            import torch  # noqa: F401
-        except ImportError:  # pragma: no cover
-            pass
+        from ._args import torch_or_none   # here, not at the top: _args imports this module
+        torch_or_none()
         if not os.path.exists(LIB_PATH):
             raise ImportError(
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "

@@ -47,7 +47,8 @@ import numpy as np
 import sys
 import threading
 
-from ._lib import P32, P64, QK_E_CAPACITY, check, lib
+from ._args import _device_array, retry_capacity
+from ._lib import P32, P64, check, lib
 
 
 # --------------------------------------------------------------------------
@@ -262,7 +263,6 @@ class Comm:
 
     @staticmethod
     def _arrays(tensors, bits):
-        from .quack import _device_array
         n = len(tensors)
         ptrs, lens, streams = (C.c_void_p * n)(), (C.c_size_t * n)(), (C.c_void_p * n)()
         for i, t in enumerate(tensors):
@@ -295,16 +295,15 @@ class Comm:
         assert len(logs) == self.nlocal
         ptrs, lens, streams = self._arrays(logs, bits)
         f = getattr(lib(), f"qk_u{bits}_decode_sharded")
-        while True:
+
+        def attempt(cap):
             hits = (C.c_uint64 * max(cap, 1))()
             nh = C.c_size_t()
             rc = f(self.handle, diff._buf if diff is not None else None, root, ptrs, lens, int(stop_at_last), hits,
                    cap, C.byref(nh), streams)
-            if rc == QK_E_CAPACITY:
-                cap = nh.value
-                continue
-            check(rc, "decode_sharded")
-            return [int(h) for h in hits[: nh.value]]
+            return rc, nh.value, (hits, nh.value)
+        hits, nh = retry_capacity(attempt, cap, "decode_sharded")
+        return [int(h) for h in hits[:nh]]
 
 
 # --------------------------------------------------------------------------

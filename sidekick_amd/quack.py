@@ -35,6 +35,10 @@ plus the batch entry points of the MI355X engine:
 Per-packet insert/remove stay on the host (one insert is far cheaper than a
 kernel launch); every batch call runs the gfx950 kernels and raises if the
 device or the library is unavailable -- there is no CPU fallback.
+
+This module is the public surface: what each call means, the order in which
+its arguments are judged, and the library call.  How an argument becomes what
+the library takes is written once, in _args.py.
 """
 from __future__ import annotations
 
@@ -45,7 +49,10 @@ import numpy as np
 
 from dataclasses import dataclass
 
-from ._lib import (P32, P64, QK_E_CAPACITY, QK_E_INVAL, QK_E_MISMATCH, QuackError, check, lib)
+from ._args import (Records, _device_array, _host_array, csr, csr_drain, dev_index, is_record_tensor,
+                    need_torch, packet_batch, ptr, retry_capacity, split_hits, stream_of, uint_len, uint_on_device)
+from ._lib import (P32, P64, QK_E_CAPACITY, QK_E_INVAL, QK_E_MISMATCH, SND_ADVANCED, SND_RESET_EXCEEDS, SND_RESET_REORDERED,
+                   SND_RESET_RETX, QuackError, check, lib)
 
 __all__ = [
     "PowerSumQuackU32", "PowerSumQuackU64", "ModularInteger", "CoefficientVector",
@@ -125,6 +132,18 @@ def get_context(device: int = 0) -> Context:
         return ctx
 
 
+def _context(ctx, *tensors) -> Context:
+    """`ctx or get_context(dev)` where dev has yet to be found: that of the
+    first CUDA tensor among the arguments, else 0.  Called first, so that with
+    no device a wrapper raises QK_E_NO_DEVICE whatever its arguments are."""
+    if ctx is not None:
+        return ctx
+    for a in tensors:
+        if getattr(a, "is_cuda", False):
+            return get_context(dev_index(a))
+    return get_context(0)
+
+
 # --------------------------------------------------------------------------
 # Field values and coefficient vectors
 # --------------------------------------------------------------------------
@@ -176,9 +195,6 @@ class _Arithmetic:
 arithmetic = _Arithmetic()
 
 
-# --------------------------------------------------------------------------
-# Array plumbing (torch device tensors, numpy host arrays)
-# --------------------------------------------------------------------------
 def roots(coeffs, bits: int = 32) -> list:
     """The distinct roots in GF(p), ascending, of z^d + c_1 z^(d-1) + ... + c_d
     (qk_u32_roots / qk_u64_roots, roots.cpp): a log entry is a root-test hit
@@ -192,41 +208,12 @@ def roots(coeffs, bits: int = 32) -> list:
     return [int(v) for v in out[:k.value]]
 
 
-def _device_array(a, bits: int):
-    """(ptr, n, device_index, stream_ptr) of a contiguous CUDA tensor, or None."""
-    try:
-        import torch
-    except ImportError:  # pragma: no cover
-        return None
-    if not isinstance(a, torch.Tensor):
-        return None
-    if not a.is_cuda:
-        raise TypeError("CPU torch tensors are not accepted; pass a numpy array for the host path")
-    ok = {32: (torch.int32, getattr(torch, "uint32", None)), 64: (torch.int64, getattr(torch, "uint64", None))}[bits]
-    if a.dtype not in ok:
-        raise TypeError(f"u{bits} ids must be a torch int{bits}/uint{bits} tensor, got {a.dtype}")
-    if not a.is_contiguous():
-        raise ValueError("ids tensor must be contiguous")
-    dev = a.device.index if a.device.index is not None else torch.cuda.current_device()
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    return a.data_ptr(), a.numel(), dev, stream
-
-
-def _host_array(a, bits: int) -> np.ndarray:
-    dt = np.uint32 if bits == 32 else np.uint64
-    arr = np.asarray(a)
-    if arr.dtype != dt:
-        arr = arr.astype(dt)
-    return np.ascontiguousarray(arr)
-
-
 # --------------------------------------------------------------------------
 # The sketch
 # --------------------------------------------------------------------------
 class _PowerSumQuack:
     BITS = 32
     _ELEM = C.c_uint32
-    _P = P32
     _pre = "qk_u32_"
 
     def __init__(self, threshold: int):
@@ -244,6 +231,18 @@ class _PowerSumQuack:
     @classmethod
     def new(cls, threshold: int):
         return cls(threshold)
+
+    @classmethod
+    def _from_record(cls, raw: bytes, threshold: int):
+        """The sketch whose record (the qk_u32 / qk_u64 image, as _buf holds it) is `raw`."""
+        q = cls.__new__(cls)
+        q._t = threshold
+        q._buf = C.create_string_buffer(raw, len(raw))
+        return q
+
+    def _record_i32(self) -> np.ndarray:
+        """The record as int32 words (a view of _buf): a row of a record tensor."""
+        return np.frombuffer(self._buf, dtype=np.int32)
 
     def _hdr(self):
         return np.frombuffer(self._buf, dtype=np.uint32, count=4)
@@ -268,7 +267,7 @@ class _PowerSumQuack:
             return [int(v) for v in np.frombuffer(self._buf, dtype=np.uint32, count=self._t, offset=16)]
         return [int(v) for v in np.frombuffer(self._buf, dtype=np.uint64, count=self._t, offset=24)]
 
-    def clone(self):
+    def clone(self):   # _from_record written out: one call less on the per-packet path
         q = type(self).__new__(type(self))
         q._t = self._t
         q._buf = C.create_string_buffer(self._buf.raw, len(self._buf))
@@ -335,9 +334,8 @@ class _PowerSumQuack:
             raise QuackError(-2, "insert_batch into a threshold-0 quACK")
         dev = _device_array(ids, self.BITS)
         if dev is not None:
-            ptr, n, d, stream = dev
-            ctx = ctx or get_context(d)
-            check(self._f("encode_device")(ctx.handle, ptr, n, self._buf, stream), "encode_device")
+            p, n, d, stream = dev
+            check(self._f("encode_device")((ctx or get_context(d)).handle, p, n, self._buf, stream), "encode_device")
             return
         arr = _host_array(ids, self.BITS)
         ctx = ctx or get_context(0)
@@ -359,30 +357,26 @@ class _PowerSumQuack:
         coeffs = list(coeffs)
         d = len(coeffs)
         carr = (self._ELEM * max(d, 1))(*coeffs)
-        keep = None
         dev = _device_array(log, self.BITS)
-        if dev is None:
-            import torch  # device memory for a host log: one H2D copy, then the GPU test
-            arr = _host_array(log, self.BITS)
-            keep = torch.from_numpy(arr.view(np.int32 if self.BITS == 32 else np.int64)).cuda()
+        if dev is None:   # device memory for a host log: one H2D copy, then the GPU test
+            keep = uint_on_device(log, "cuda", "log", self.BITS)
             dev = _device_array(keep, self.BITS)
-        ptr, n, dv, stream = dev
+        lptr, n, dv, stream = dev
         ctx = ctx or get_context(dv)
         stop_idx = C.c_uint64(n)
-        while True:
+
+        def attempt(cap):
             hits = (C.c_uint64 * max(cap, 1))()
             nh = C.c_size_t()
-            args = (ctx.handle, carr, d, ptr, n, int(stop_value is not None), int(stop_value or 0), hits, cap,
+            args = (ctx.handle, carr, d, lptr, n, int(stop_value is not None), int(stop_value or 0), hits, cap,
                     C.byref(nh))
             if shard:
                 rc = self._f("root_test_shard_device")(*args, C.byref(stop_idx), stream)
             else:
                 rc = self._f("root_test_device")(*args, stream)
-            if rc == QK_E_CAPACITY:
-                cap = nh.value
-                continue
-            check(rc, "root_test_device")
-            return [int(h) for h in hits[: nh.value]], int(stop_idx.value)
+            return rc, nh.value, (hits, nh.value)
+        hits, nh = retry_capacity(attempt, cap, "root_test_device")
+        return [int(h) for h in hits[:nh]], int(stop_idx.value)
 
     def decode_host(self, log, stop_at_last: bool = False) -> list:
         """Positions of the missing entries of a HOST log (numpy / sequence),
@@ -390,17 +384,16 @@ class _PowerSumQuack:
         cut at the first entry equal to last_value() when stop_at_last
         (media_client.rs:304-313).  For the short logs a receiver holds."""
         arr = _host_array(log, self.BITS)
-        ptr = arr.ctypes.data_as(C.POINTER(self._ELEM))
+        p = arr.ctypes.data_as(C.POINTER(self._ELEM))
         cap = max(self._t, 1)
-        while True:
+        while True:   # ptr and retry_capacity written out: the receiver calls this per quACK, and each hop showed
             hits = (C.c_uint64 * cap)()
             nh = C.c_size_t()
-            rc = self._f("decode_host")(self._buf, ptr, arr.size, int(stop_at_last), hits, cap, C.byref(nh))
-            if rc == QK_E_CAPACITY:
-                cap = nh.value
-                continue
-            check(rc, "decode_host")
-            return [int(h) for h in hits[: nh.value]]
+            rc = self._f("decode_host")(self._buf, p, arr.size, int(stop_at_last), hits, cap, C.byref(nh))
+            if rc != QK_E_CAPACITY:
+                check(rc, "decode_host")
+                return [int(h) for h in hits[: nh.value]]
+            cap = nh.value
 
     def decode_with_log(self, log, ctx: Context | None = None) -> list:
         """quack's decode_with_log: the ids of `log` that are missing (every
@@ -411,7 +404,7 @@ class _PowerSumQuack:
         pos = self.root_test(coeffs, log, ctx=ctx)
         dev = _device_array(log, self.BITS)
         if dev is not None:
-            import torch
+            torch = need_torch()
             idx = torch.tensor(pos, dtype=torch.int64, device=log.device)
             vals = log[idx].cpu().numpy()
         else:
@@ -424,7 +417,6 @@ class PowerSumQuackU32(_PowerSumQuack):
     """quack::PowerSumQuackU32 — u32 ids over GF(2^32 - 5)."""
     BITS = 32
     _ELEM = C.c_uint32
-    _P = P32
     _pre = "qk_u32_"
 
 
@@ -432,7 +424,6 @@ class PowerSumQuackU64(_PowerSumQuack):
     """quack::PowerSumQuackU64 — u64 ids over GF(2^64 - 59)."""
     BITS = 64
     _ELEM = C.c_uint64
-    _P = P64
     _pre = "qk_u64_"
 
 
@@ -454,22 +445,12 @@ def encode_packets(q: "PowerSumQuackU32", bufs, stride: int = 67, meta=None, my_
     uint8 tensor of n*stride bytes (records), `meta` an optional CUDA tensor
     of n 8-byte qk_pkt_meta records (int64 view), `my_ipv4` 4 ints or None.
     Updates q in place (reset if a packet to my_ipv4 is seen); returns stats."""
-    import torch
-    if not (isinstance(bufs, torch.Tensor) and bufs.is_cuda and bufs.dtype == torch.uint8 and bufs.is_contiguous()):
-        raise TypeError("bufs must be a contiguous CUDA uint8 tensor")
-    n = bufs.numel() // stride
-    dev = bufs.device.index if bufs.device.index is not None else torch.cuda.current_device()
+    n, dev, mptr = packet_batch(bufs, stride, meta)
     ctx = ctx or get_context(dev)
-    mptr = None
-    if meta is not None:
-        if not (meta.is_cuda and meta.is_contiguous() and meta.numel() * meta.element_size() == 8 * n):
-            raise ValueError("meta must be a contiguous CUDA tensor of n 8-byte records")
-        mptr = meta.data_ptr()
     ip = (C.c_uint8 * 4)(*my_ipv4) if my_ipv4 is not None else None
     st = PktStats()
     check(lib().qk_u32_encode_packets_device(ctx.handle, bufs.data_ptr(), n, stride, mptr, ip, q._buf,
-                                              C.byref(st), torch.cuda.current_stream(dev).cuda_stream),
-          "encode_packets")
+                                              C.byref(st), stream_of(bufs)), "encode_packets")
     return {k: getattr(st, k) for k, _ in PktStats._fields_}
 
 
@@ -477,56 +458,25 @@ class FlowKey(C.Structure):
     _fields_ = [("addr", C.c_uint8 * 12)]
 
 
+_quack_from_bytes = PowerSumQuackU32._from_record   # the name tests/test_gpu_wire.py imports
+
+
+def _quacks_from_records(raw: bytes, rec: int, n: int, threshold: int) -> list:
+    """The PowerSumQuackU32 of the first n records, of `rec` bytes each, of `raw`."""
+    return [PowerSumQuackU32._from_record(raw[i * rec:(i + 1) * rec], threshold) for i in range(n)]
+
+
 def encode_segments(ids, offsets, threshold: int, ctx: Context | None = None) -> list:
     """Segmented encode: `ids` a CUDA u32 tensor grouped by flow, `offsets`
     nseg+1 ints (CSR).  Returns one PowerSumQuackU32 per segment."""
-    ptr, n, dev, stream = _device_array(ids, 32)
+    iptr, n, dev, stream = _device_array(ids, 32)
     ctx = ctx or get_context(dev)
-    offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64))
-    nseg = len(offs) - 1
+    offs, nseg = csr(offsets, "ids")
     rec = lib().qk_u32_size(threshold)
     out = C.create_string_buffer(max(nseg, 1) * rec)
-    check(lib().qk_u32_encode_segments_device(ctx.handle, ptr, offs.ctypes.data_as(C.POINTER(C.c_uint64)), nseg,
-                                               threshold, out, stream), "encode_segments")
-    res = []
-    raw = out.raw                     # one copy (ctypes .raw copies the whole buffer per access)
-    for i in range(nseg):
-        q = PowerSumQuackU32.__new__(PowerSumQuackU32)
-        q._t = threshold
-        q._buf = C.create_string_buffer(raw[i * rec:(i + 1) * rec], rec)
-        res.append(q)
-    return res
-
-
-def _segment_records(diffs, threshold):
-    """(pointer, nseg, threshold, device index or None, keep-alive) of a batch
-    of diff sketches: a list of PowerSumQuackU32 of one threshold (packed into
-    host records) or a CUDA int32 tensor [nseg, 4 + t] of qk_u32 records, as
-    encode_flows(device_out=True) returns."""
-    try:
-        import torch
-    except ImportError:  # pragma: no cover
-        torch = None
-    if torch is not None and isinstance(diffs, torch.Tensor):
-        if not (diffs.is_cuda and diffs.dtype == torch.int32 and diffs.dim() == 2 and diffs.is_contiguous()
-                and diffs.shape[1] > 4):
-            raise TypeError("device diffs must be a contiguous CUDA int32 tensor [nseg, 4 + t]")
-        t = diffs.shape[1] - 4 if threshold is None else int(threshold)
-        if t != diffs.shape[1] - 4:
-            raise QuackError(QK_E_MISMATCH, "device diffs: record width is not 4 + threshold")
-        dev = diffs.device.index if diffs.device.index is not None else torch.cuda.current_device()
-        return diffs.data_ptr(), diffs.shape[0], t, dev, diffs
-    diffs = list(diffs)
-    if not diffs:
-        return None, 0, int(threshold) if threshold is not None else 1, None, None
-    t = diffs[0].threshold() if threshold is None else int(threshold)
-    for q in diffs:
-        if not isinstance(q, PowerSumQuackU32):
-            raise TypeError("diffs must be PowerSumQuackU32 sketches (the batched decode is u32 only)")
-        if q.threshold() != t:
-            raise QuackError(QK_E_MISMATCH, "diffs of different thresholds")
-    buf = C.create_string_buffer(b"".join(q._buf.raw for q in diffs))
-    return C.cast(buf, C.c_void_p), len(diffs), t, None, buf
+    check(lib().qk_u32_encode_segments_device(ctx.handle, iptr, ptr(offs), nseg, threshold, out, stream),
+          "encode_segments")
+    return _quacks_from_records(out.raw, rec, nseg, threshold)
 
 
 def to_coeffs_segments(diffs, threshold: int | None = None, ctx: Context | None = None):
@@ -535,20 +485,15 @@ def to_coeffs_segments(diffs, threshold: int | None = None, ctx: Context | None 
     sidekick_multi.rs:65-90).  Returns (coeffs, status): one CoefficientVector
     per sketch (empty where status is QK_E_UNDECODABLE, count > threshold) and
     the per-sketch status codes."""
-    ptr, nseg, t, dev, keep = _segment_records(diffs, threshold)
-    ctx = ctx or get_context(dev or 0)
-    stream = None
-    if dev is not None:
-        import torch
-        stream = torch.cuda.current_stream(dev).cuda_stream
+    r = Records.parse(diffs, PowerSumQuackU32, threshold)
+    ctx = ctx or get_context(r.dev or 0)
+    nseg, t = r.nseg, r.t
     coeffs = np.zeros((max(nseg, 1), t), dtype=np.uint32)
     deg = np.zeros(max(nseg, 1), dtype=np.uint32)
     status = np.zeros(max(nseg, 1), dtype=np.int32)
-    check(lib().qk_u32_to_coeffs_segments_device(ctx.handle, ptr, nseg, t, coeffs.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                  deg.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                                  status.ctypes.data_as(C.POINTER(C.c_int32)), stream),
+    check(lib().qk_u32_to_coeffs_segments_device(ctx.handle, r.ptr, nseg, t, ptr(coeffs), ptr(deg), ptr(status),
+                                                  stream_of(r.keep, r.dev) if r.dev is not None else None),
           "to_coeffs_segments")
-    del keep
     return ([CoefficientVector(coeffs[g, :deg[g]].tolist(), 32) for g in range(nseg)],
             [int(s) for s in status[:nseg]])
 
@@ -562,42 +507,32 @@ def decode_segments(diffs, log, offsets, stop_at_last: bool = False, ctx: Contex
     positions[g] are the positions, local to segment g, of its missing
     entries, equal to diffs[g].decode_host(log[offsets[g]:offsets[g+1]],
     stop_at_last); status[g] is QK_OK or QK_E_UNDECODABLE (no positions)."""
-    ptr, nseg, t, _, keep = _segment_records(diffs, None)
-    d_log = _device_array(log, 32)
-    if d_log is None:
-        import torch  # a host log: one H2D copy (raises with no device: there is no CPU path)
-        ctx = ctx or get_context(0)
-        log = torch.from_numpy(_host_array(log, 32).view(np.int32)).to(f"cuda:{ctx.device}")
-        d_log = _device_array(log, 32)
-    lptr, n, dev, stream = d_log
-    ctx = ctx or get_context(dev)
-    offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64))
-    if len(offs) != nseg + 1:
-        raise ValueError("offsets must hold one entry more than diffs")
-    if nseg and int(offs[-1]) > n:
-        raise ValueError("offsets run past the end of log")
+    r = Records.parse(diffs, PowerSumQuackU32)
+    nseg = r.nseg
+    ctx, log, (lptr, n, _, stream) = _log_on_device(log, ctx)
+    offs, _ = csr(offsets, "diffs", nseg, n)
     hoffs = np.zeros(nseg + 1, dtype=np.uint64)
     status = np.zeros(max(nseg, 1), dtype=np.int32)
-    cap = max(1024, 4 * nseg)
-    while True:
+
+    def attempt(cap):
         hits = np.empty(max(cap, 1), dtype=np.uint64)
         nh = C.c_size_t()
-        rc = lib().qk_u32_decode_segments_device(ctx.handle, ptr, lptr, offs.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                                 nseg, t, int(bool(stop_at_last)),
-                                                 hits.ctypes.data_as(C.POINTER(C.c_uint64)), cap,
-                                                 hoffs.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                                 status.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(nh), stream)
-        if rc == QK_E_CAPACITY:
-            cap = nh.value
-            continue
-        check(rc, "decode_segments")
-        break
-    del keep
-    out = []
-    for g in range(nseg):
-        a, b = int(hoffs[g]), int(hoffs[g + 1])
-        out.append((hits[a:b] - offs[g]).tolist())
-    return out, [int(s) for s in status[:nseg]]
+        rc = lib().qk_u32_decode_segments_device(ctx.handle, r.ptr, lptr, ptr(offs), nseg, r.t, int(bool(stop_at_last)),
+                                                 ptr(hits), cap, ptr(hoffs), ptr(status), C.byref(nh), stream)
+        return rc, nh.value, hits
+    hits = retry_capacity(attempt, max(1024, 4 * nseg), "decode_segments")
+    return split_hits(hits, hoffs, offs), [int(s) for s in status[:nseg]]
+
+
+def _log_on_device(log, ctx):
+    """(context, log tensor, its _device_array): a CUDA u32/int32 log as it is, a host
+    one uploaded (one H2D copy; no device: QK_E_NO_DEVICE, there is no CPU path)."""
+    d_log = _device_array(log, 32)
+    if d_log is None:
+        ctx = ctx or get_context(0)
+        log = uint_on_device(log, f"cuda:{ctx.device}", "log")
+        d_log = _device_array(log, 32)
+    return ctx or get_context(d_log[2]), log, d_log
 
 
 @dataclass
@@ -607,25 +542,6 @@ class SenderStep:
     action: np.ndarray    # np.uint8: SND_IDLE, SND_ADVANCED, or the OR of the SND_RESET_* bits
     drain: np.ndarray     # np.uint64: log entries to drop (drain_segments)
     missing: list         # per flow, the segment-local positions to retransmit, ascending
-
-
-def _record_tensor(recs, what: str, ctx_box: list, ctx):
-    """`recs` as a CUDA int32 record tensor [nseg, 4 + t]: a device tensor as it
-    is, a list of PowerSumQuackU32 of one threshold uploaded.  The context is
-    resolved (ctx_box[0]) before the upload: with no device that raises
-    QK_E_NO_DEVICE."""
-    ptr, nseg, t, dev, keep = _segment_records(recs, None)
-    if dev is not None:
-        if ctx_box[0] is None:
-            ctx_box[0] = ctx or get_context(dev)
-        return recs, nseg, t
-    if nseg == 0:
-        raise ValueError(f"{what}: an empty list of sketches has no threshold; pass a record tensor")
-    if ctx_box[0] is None:
-        ctx_box[0] = ctx or get_context(0)
-    import torch
-    host = np.frombuffer(keep, dtype=np.int32, count=nseg * (4 + t)).reshape(nseg, 4 + t)
-    return torch.from_numpy(host.copy()).to(f"cuda:{ctx_box[0].device}"), nseg, t
 
 
 def sender_step(mine, peer, log, offsets, present=None, ctx: Context | None = None) -> SenderStep:
@@ -641,28 +557,28 @@ def sender_step(mine, peer, log, offsets, present=None, ctx: Context | None = No
     tested (a reset keeps the prefix insert and decodes nothing), otherwise
     mine - peer is decoded against the segment and every missing id removed
     from mine.  The reset debounce stays with the caller."""
-    box = [None]
-    d_mine, nseg, t = _record_tensor(mine, "mine", box, ctx)
-    d_peer, npeer, tp = _record_tensor(peer, "peer", box, ctx)
-    if tp != t:
+    # what the host alone can judge, then the context (no device: QK_E_NO_DEVICE), then the uploads
+    r_mine = Records.parse(mine, PowerSumQuackU32)
+    r_mine.need_threshold("mine")
+    r_peer = Records.parse(peer, PowerSumQuackU32)
+    r_peer.need_threshold("peer")
+    nseg, t = r_mine.nseg, r_mine.t
+    if r_peer.t != t:
         raise QuackError(QK_E_MISMATCH, "mine and peer of different thresholds")
-    if npeer != nseg:
+    if r_peer.nseg != nseg:
         raise ValueError("mine and peer must hold one record per flow")
-    ctx = box[0]
-    import torch
+    ctx = ctx or get_context(r_mine.dev or 0)
+    d_mine, d_peer = r_mine.to_device(ctx, "mine"), r_peer.to_device(ctx, "peer")
+    torch = need_torch()
     device = d_mine.device
     if d_peer.device != device:
         raise ValueError("mine and peer on different devices")
     d_log = _device_array(log, 32)
     if d_log is None:
-        log = torch.from_numpy(_host_array(log, 32).view(np.int32)).to(device)
+        log = uint_on_device(log, device, "log")
         d_log = _device_array(log, 32)
     lptr, n, _, stream = d_log
-    offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64))
-    if len(offs) != nseg + 1:
-        raise ValueError("offsets must hold one entry more than mine")
-    if nseg and int(offs[-1]) > n:
-        raise ValueError("offsets run past the end of log")
+    offs, _ = csr(offsets, "mine", nseg, n)
     d_present = None
     if present is not None:
         if isinstance(present, torch.Tensor):
@@ -677,26 +593,17 @@ def sender_step(mine, peer, log, offsets, present=None, ctx: Context | None = No
     action = np.zeros(max(nseg, 1), dtype=np.uint8)
     drain = np.zeros(max(nseg, 1), dtype=np.uint64)
     hoffs = np.zeros(nseg + 1, dtype=np.uint64)
-    cap = max(1024, 4 * nseg)
-    while True:
+
+    def attempt(cap):
         hits = np.empty(max(cap, 1), dtype=np.uint64)
         nh = C.c_size_t()
         rc = lib().qk_u32_sender_step_segments_device(
             ctx.handle, d_mine.data_ptr(), d_peer.data_ptr(), d_present.data_ptr() if d_present is not None else None,
-            lptr, offs.ctypes.data_as(C.POINTER(C.c_uint64)), nseg, t, mine_out.data_ptr(),
-            action.ctypes.data_as(C.POINTER(C.c_uint8)), drain.ctypes.data_as(C.POINTER(C.c_uint64)),
-            hits.ctypes.data_as(C.POINTER(C.c_uint64)), cap, hoffs.ctypes.data_as(C.POINTER(C.c_uint64)),
+            lptr, ptr(offs), nseg, t, mine_out.data_ptr(), ptr(action), ptr(drain), ptr(hits), cap, ptr(hoffs),
             C.byref(nh), stream)
-        if rc == QK_E_CAPACITY:
-            cap = nh.value
-            continue
-        check(rc, "sender_step")
-        break
-    missing = []
-    for g in range(nseg):
-        a, b = int(hoffs[g]), int(hoffs[g + 1])
-        missing.append((hits[a:b] - offs[g]).tolist())
-    return SenderStep(mine_out, action[:nseg], drain[:nseg], missing)
+        return rc, nh.value, hits
+    hits = retry_capacity(attempt, max(1024, 4 * nseg), "sender_step")
+    return SenderStep(mine_out, action[:nseg], drain[:nseg], split_hits(hits, hoffs, offs))
 
 
 def drain_segments(log, offsets, drain, aux=None, ctx: Context | None = None):
@@ -706,14 +613,9 @@ def drain_segments(log, offsets, drain, aux=None, ctx: Context | None = None):
     without its first drain[g] entries.  `aux`: an optional parallel tensor
     (the seqnos), moved alike.  Returns (log_out, offsets_out) or (log_out,
     offsets_out, aux_out)."""
-    offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64))
-    dr = np.ascontiguousarray(np.asarray(drain, dtype=np.uint64))
-    nseg = len(offs) - 1
-    if nseg < 0 or len(dr) != nseg:
-        raise ValueError("offsets must hold one entry more than drain")
-    lens = offs[1:] - offs[:-1]
-    if np.any(offs[1:] < offs[:-1]) or np.any(dr > lens):
-        raise QuackError(QK_E_INVAL, "drain_segments: drain[g] exceeds the segment's length")
+    if drain is None:
+        raise TypeError("drain must hold one count per segment")
+    offs, nseg, dr, lens = csr_drain(offsets, drain, "drain_segments")
     d_log = _device_array(log, 32)
     if d_log is None:
         raise TypeError("log must be a CUDA u32/int32 tensor")
@@ -725,35 +627,16 @@ def drain_segments(log, offsets, drain, aux=None, ctx: Context | None = None):
         if d_aux is None or d_aux[1] != n or aux.device != log.device:
             raise TypeError("aux must be a CUDA u32/int32 tensor as long as log, on its device")
     ctx = ctx or get_context(dev)
-    import torch
+    torch = need_torch()
     left = int((lens - dr).sum())
     out = torch.empty((left,), dtype=log.dtype, device=log.device)
     aux_out = torch.empty((left,), dtype=aux.dtype, device=log.device) if aux is not None else None
     offs_out = np.zeros(nseg + 1, dtype=np.uint64)
     check(lib().qk_u32_log_drain_segments_device(
-        ctx.handle, lptr, d_aux[0] if aux is not None and left else None, offs.ctypes.data_as(C.POINTER(C.c_uint64)),
-        dr.ctypes.data_as(C.POINTER(C.c_uint64)), nseg, out.data_ptr() if left else None,
-        aux_out.data_ptr() if aux is not None and left else None, left,
-        offs_out.ctypes.data_as(C.POINTER(C.c_uint64)), stream), "drain_segments")
+        ctx.handle, lptr, d_aux[0] if aux is not None and left else None, ptr(offs), ptr(dr), nseg,
+        out.data_ptr() if left else None, aux_out.data_ptr() if aux is not None and left else None, left,
+        ptr(offs_out), stream), "drain_segments")
     return (out, offs_out) if aux is None else (out, offs_out, aux_out)
-
-
-def _u32_len(a, what: str) -> int:
-    try:
-        return int(a.numel()) if hasattr(a, "numel") else len(a)
-    except TypeError:
-        raise TypeError(f"{what} must be a CUDA u32/int32 tensor or a host array") from None
-
-
-def _u32_on_device(a, device, what: str):
-    """`a` as a contiguous CUDA int32/uint32 tensor: a CUDA tensor as it is, a
-    host array uploaded."""
-    import torch
-    if isinstance(a, torch.Tensor):
-        if _device_array(a, 32) is None or a.device != device:
-            raise TypeError(f"{what} must be a CUDA u32/int32 tensor on the log's device, or a host array")
-        return a
-    return torch.from_numpy(_host_array(a, 32).view(np.int32)).to(device)
 
 
 def update_segments(log, offsets, drain, new_flow, new_ids, aux=None, new_aux=None, ctx: Context | None = None):
@@ -768,59 +651,44 @@ def update_segments(log, offsets, drain, new_flow, new_ids, aux=None, new_aux=No
     `log`, `aux` and the three new_* arrays are CUDA u32/int32 tensors, or host
     arrays, which are uploaded.  Returns (log_out, offsets_out) or (log_out,
     offsets_out, aux_out), as drain_segments does."""
-    offs = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64))
-    nseg = len(offs) - 1
-    if nseg < 0:
-        raise ValueError("offsets must hold at least one entry")
-    lens = offs[1:] - offs[:-1]
-    dr = None
-    if drain is not None:
-        dr = np.ascontiguousarray(np.asarray(drain, dtype=np.uint64))
-        if len(dr) != nseg:
-            raise ValueError("offsets must hold one entry more than drain")
-    if np.any(offs[1:] < offs[:-1]) or (dr is not None and np.any(dr > lens)):
-        raise QuackError(QK_E_INVAL, "update_segments: drain[g] exceeds the segment's length")
-    n_new = _u32_len(new_flow, "new_flow")
-    if _u32_len(new_ids, "new_ids") != n_new:
+    offs, nseg, dr, lens = csr_drain(offsets, drain, "update_segments")
+    n_new = uint_len(new_flow, "new_flow")
+    if uint_len(new_ids, "new_ids") != n_new:
         raise ValueError("new_flow and new_ids must be equally long")
     if (aux is None) != (new_aux is None):
         raise ValueError("aux and new_aux go together")
-    if new_aux is not None and _u32_len(new_aux, "new_aux") != n_new:
+    if new_aux is not None and uint_len(new_aux, "new_aux") != n_new:
         raise ValueError("new_flow and new_aux must be equally long")
-    import torch
-    if isinstance(log, torch.Tensor):
-        d_log = _device_array(log, 32)
-        ctx = ctx or get_context(d_log[2])
-    else:   # a host log is uploaded; with no device this raises QK_E_NO_DEVICE
-        ctx = ctx or get_context(0)
-        log = torch.from_numpy(_host_array(log, 32).view(np.int32)).to(f"cuda:{ctx.device}")
-        d_log = _device_array(log, 32)
-    lptr, n, _, stream = d_log
-    device = log.device
+    ctx, log, (lptr, n, _, stream) = _log_on_device(log, ctx)
+    torch, device = need_torch(), log.device
     if nseg and int(offs[-1]) > n:
         raise ValueError("offsets run past the end of log")
     if aux is not None:
-        aux = _u32_on_device(aux, device, "aux")
+        aux = uint_on_device(aux, device, "aux")
         if aux.numel() != n:
             raise TypeError("aux must be as long as log")
-        new_aux = _u32_on_device(new_aux, device, "new_aux")
-    new_flow = _u32_on_device(new_flow, device, "new_flow")
-    new_ids = _u32_on_device(new_ids, device, "new_ids")
+        new_aux = uint_on_device(new_aux, device, "new_aux")
+    new_flow = uint_on_device(new_flow, device, "new_flow")
+    new_ids = uint_on_device(new_ids, device, "new_ids")
     # the result's size is known here: no capacity retry
     total = int(lens.sum()) - (int(dr.sum()) if dr is not None else 0) + n_new
     out = torch.empty((total,), dtype=log.dtype, device=device)
     aux_out = torch.empty((total,), dtype=aux.dtype, device=device) if aux is not None else None
     offs_out = np.zeros(nseg + 1, dtype=np.uint64)
-    u64 = C.POINTER(C.c_uint64)
     has_in = nseg > 0 and int(offs[-1]) > int(offs[0])
     check(lib().qk_u32_log_update_segments_device(
         ctx.handle, lptr if has_in else None, aux.data_ptr() if aux is not None and has_in and total else None,
-        offs.ctypes.data_as(u64), dr.ctypes.data_as(u64) if dr is not None else None, nseg,
+        ptr(offs), ptr(dr) if dr is not None else None, nseg,
         new_flow.data_ptr() if n_new else None, new_ids.data_ptr() if n_new else None,
         new_aux.data_ptr() if aux is not None and n_new else None, n_new, out.data_ptr() if total else None,
-        aux_out.data_ptr() if aux is not None and total else None, total, offs_out.ctypes.data_as(u64), stream),
+        aux_out.data_ptr() if aux is not None and total else None, total, ptr(offs_out), stream),
         "update_segments")
     return (out, offs_out) if aux is None else (out, offs_out, aux_out)
+
+
+def _fresh_record(threshold: int, device):
+    """The record of an empty PowerSumQuackU32, on the device: int32 [4 + t]."""
+    return need_torch().from_numpy(PowerSumQuackU32(threshold)._record_i32().copy()).to(device)
 
 
 @dataclass
@@ -847,10 +715,9 @@ class DeviceSenderLog:
         self.threshold = int(threshold)
         self.reset_debounce_s = reset_debounce_s
         self._ctx = get_context(device)          # no device: QK_E_NO_DEVICE, nothing falls back
-        import torch
+        torch = need_torch()
         self._device = torch.device(f"cuda:{device}")
-        self._fresh = torch.from_numpy(
-            np.frombuffer(PowerSumQuackU32(self.threshold)._buf, dtype=np.int32).copy()).to(self._device)
+        self._fresh = _fresh_record(self.threshold, self._device)
         self.log = torch.empty((0,), dtype=torch.int32, device=self._device)
         self.seqnos = torch.empty((0,), dtype=torch.int32, device=self._device)
         self.mine = torch.empty((0, 4 + self.threshold), dtype=torch.int32, device=self._device)
@@ -866,7 +733,7 @@ class DeviceSenderLog:
 
     def add_flows(self, k: int) -> None:
         """k more flows, each with an empty log and a fresh quACK."""
-        import torch
+        torch = need_torch()
         k = int(k)
         if k < 0:
             raise ValueError("k must not be negative")
@@ -884,8 +751,8 @@ class DeviceSenderLog:
     def send(self, flow, seqno, ids) -> None:
         """on_send(seqno, id) on flow[i] for every i, in this order; applies a
         pending drain in the same pass."""
-        n = _u32_len(flow, "flow")
-        if _u32_len(seqno, "seqno") != n or _u32_len(ids, "ids") != n:
+        n = uint_len(flow, "flow")
+        if uint_len(seqno, "seqno") != n or uint_len(ids, "ids") != n:
             raise ValueError("flow, seqno and ids must be equally long")
         self._update(flow, seqno, ids)
 
@@ -899,8 +766,7 @@ class DeviceSenderLog:
     def on_quacks(self, peer, present=None, now: float = 0.0) -> SenderLogStep:
         """on_quack(peer[g], now) on every flow g with present[g] (None: all):
         one sender step, the reset debounce of receiver.py:86-94 on the host."""
-        import torch
-        from ._lib import SND_ADVANCED
+        torch = need_torch()
         self.flush()
         nf = self.nflows
         res = sender_step(self.mine, peer, self.log, self.offsets, present=present, ctx=self._ctx)
@@ -919,7 +785,8 @@ class DeviceSenderLog:
             last[fired] = now
         last[action == SND_ADVANCED] = np.nan                               # :280-283
         self._pending = drain if drain.any() else None
-        reason = [((a & 2) != 0, (a & 4) != 0, (a & 8) != 0) if b else () for a, b in zip(action.tolist(), bits.tolist())]
+        reason = [((a & SND_RESET_REORDERED) != 0, (a & SND_RESET_RETX) != 0, (a & SND_RESET_EXCEEDS) != 0) if b else ()
+                  for a, b in zip(action.tolist(), bits.tolist())]
         # the seqnos at the hit positions: the only log values that cross to the host
         counts = [len(m) for m in res.missing]
         retransmit = [[] for _ in range(nf)]
@@ -939,7 +806,6 @@ class DeviceSenderLog:
         on_quacks: the newest accepted quACK of every flow is stepped, no
         per-flow host work in between.  Returns (SenderLogStep, status), status
         as ingest_wire gives it."""
-        import torch
         nf = self.nflows
         if self._peer is None or self._peer.shape[0] != nf:
             old = self._peer
@@ -960,22 +826,14 @@ def encode_flows(bufs, threshold: int, stride: int = 67, meta=None, my_addr=None
     qk_u32 records), written in place by the finalize kernel.  `cap` is the
     flow count the outputs are first sized for (a batch of more flows runs a
     second time with the size the first run reports)."""
-    import torch
-    if not (isinstance(bufs, torch.Tensor) and bufs.is_cuda and bufs.dtype == torch.uint8 and bufs.is_contiguous()):
-        raise TypeError("bufs must be a contiguous CUDA uint8 tensor")
-    n = bufs.numel() // stride
-    dev = bufs.device.index if bufs.device.index is not None else torch.cuda.current_device()
+    n, dev, mptr = packet_batch(bufs, stride, meta)
     ctx = ctx or get_context(dev)
-    mptr = None
-    if meta is not None:
-        if not (meta.is_cuda and meta.is_contiguous() and meta.numel() * meta.element_size() == 8 * n):
-            raise ValueError("meta must be a contiguous CUDA tensor of n 8-byte records")
-        mptr = meta.data_ptr()
+    torch = need_torch()
     addr = (C.c_uint8 * 6)(*my_addr) if my_addr is not None else None
     rec = lib().qk_u32_size(threshold)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    cap = max(int(cap), 1)
-    while True:
+    stream = stream_of(bufs)
+
+    def attempt(cap):
         nf, st = C.c_size_t(), PktStats()
         if device_out:
             keys = torch.empty((cap, 12), dtype=torch.uint8, device=bufs.device)
@@ -987,24 +845,13 @@ def encode_flows(bufs, threshold: int, stride: int = 67, meta=None, my_addr=None
             kp, sp = keys, sk
         rc = lib().qk_u32_encode_flows_device(ctx.handle, bufs.data_ptr(), n, stride, mptr, addr, threshold, kp, sp,
                                               cap, C.byref(nf), C.byref(st), stream)
-        if rc == QK_E_CAPACITY:
-            cap = nf.value
-            continue
-        check(rc, "encode_flows")
-        break
+        return rc, nf.value, (keys, sk, nf.value, st)
+    keys, sk, m, st = retry_capacity(attempt, max(int(cap), 1), "encode_flows")
     stats = {k: getattr(st, k) for k, _ in PktStats._fields_}
-    m = nf.value
     if device_out:
         return keys[:m], sk[:m], stats
-    out_k, out_q = [], []
-    raw = sk.raw                      # one copy of the records (ctypes .raw copies the whole buffer per access)
-    for i in range(m):
-        out_k.append(bytes(keys[i].addr))
-        q = PowerSumQuackU32.__new__(PowerSumQuackU32)
-        q._t = threshold
-        q._buf = C.create_string_buffer(raw[i * rec:(i + 1) * rec], rec)
-        out_q.append(q)
-    return out_k, out_q, stats
+    # .raw: one copy of the records (ctypes .raw copies the whole buffer per access)
+    return [bytes(keys[i].addr) for i in range(m)], _quacks_from_records(sk.raw, rec, m, threshold), stats
 
 
 class FlowQuacks:
@@ -1058,34 +905,13 @@ class FlowQuacks:
 # --------------------------------------------------------------------------
 # The flow table in HBM: key-sorted flow arrays and the three device calls
 # --------------------------------------------------------------------------
-def _quack_from_bytes(raw: bytes, threshold: int) -> "PowerSumQuackU32":
-    q = PowerSumQuackU32.__new__(PowerSumQuackU32)
-    q._t = threshold
-    q._buf = C.create_string_buffer(raw, len(raw))
-    return q
-
-
-def _flow_ctx(ctx, *tensors) -> Context:
-    """The context of a flow-table call, resolved before anything else: with no
-    device this raises QK_E_NO_DEVICE whatever the arguments are."""
-    if ctx is not None:
-        return ctx
-    for a in tensors:
-        if getattr(a, "is_cuda", False):
-            import torch
-            return get_context(a.device.index if a.device.index is not None else torch.cuda.current_device())
-    return get_context(0)
-
-
 def _flow_array(keys, sk, what: str):
     """(n, threshold) of a flow array: `keys` a CUDA uint8 tensor [n, 12], `sk` a
     CUDA int32 tensor [n, 4 + t] of qk_u32 records, both contiguous, as
     encode_flows(device_out=True) returns them."""
-    import torch
-    ok = (isinstance(keys, torch.Tensor) and isinstance(sk, torch.Tensor) and keys.is_cuda and sk.is_cuda
-          and keys.dtype == torch.uint8 and sk.dtype == torch.int32 and keys.dim() == 2 and sk.dim() == 2
-          and keys.shape[1] == 12 and sk.shape[1] > 4 and keys.shape[0] == sk.shape[0]
-          and keys.is_contiguous() and sk.is_contiguous())
+    torch = need_torch()
+    ok = (is_record_tensor(sk) and isinstance(keys, torch.Tensor) and keys.is_cuda and keys.dtype == torch.uint8
+          and keys.dim() == 2 and keys.shape[1] == 12 and keys.shape[0] == sk.shape[0] and keys.is_contiguous())
     if not ok:
         raise TypeError(f"{what}: a flow array is a contiguous CUDA uint8 [n, 12] key tensor and a contiguous CUDA "
                         "int32 [n, 4 + t] record tensor of the same n")
@@ -1102,9 +928,14 @@ def _flow_pair(keys_a, sk_a, keys_b, sk_b):
     return na, nb, t
 
 
-def _flow_stream(t):
-    import torch
-    return torch.cuda.current_stream(t.device).cuda_stream
+def _flows_merge_into(ctx, ka, sa, na, kb, sb, nb, t, frequency, ko, so, do) -> int:
+    """qk_u32_flows_merge_device of flow arrays a (na rows) and b (nb rows, the
+    later stream) into the tensors ko / so / do; returns the union's row count."""
+    n = C.c_size_t()
+    check(lib().qk_u32_flows_merge_device(ctx.handle, ka.data_ptr(), sa.data_ptr(), na, kb.data_ptr(), sb.data_ptr(),
+                                          nb, t, int(frequency), ko.data_ptr(), so.data_ptr(), do.data_ptr(),
+                                          ko.shape[0], C.byref(n), stream_of(ko)), "flows_merge")
+    return n.value
 
 
 def flows_merge(keys_a, sk_a, keys_b, sk_b, frequency_pkts: int = 0, ctx: Context | None = None):
@@ -1115,19 +946,15 @@ def flows_merge(keys_a, sk_a, keys_b, sk_b, frequency_pkts: int = 0, ctx: Contex
     and a uint8 tensor flagging the flows whose count crossed a multiple of
     frequency_pkts during b (all 0 when it is 0).  The outputs are views of
     na + nb freshly allocated rows, so the call never retries."""
-    import torch
-    ctx = _flow_ctx(ctx, keys_a, keys_b)
+    ctx = _context(ctx, keys_a, keys_b)
     na, nb, t = _flow_pair(keys_a, sk_a, keys_b, sk_b)
+    torch = need_torch()
     cap = na + nb
     keys = torch.empty((cap, 12), dtype=torch.uint8, device=keys_a.device)
     sk = torch.empty((cap, 4 + t), dtype=torch.int32, device=keys_a.device)
     due = torch.empty((cap,), dtype=torch.uint8, device=keys_a.device)
-    n = C.c_size_t()
-    check(lib().qk_u32_flows_merge_device(ctx.handle, keys_a.data_ptr(), sk_a.data_ptr(), na, keys_b.data_ptr(),
-                                          sk_b.data_ptr(), nb, t, int(frequency_pkts), keys.data_ptr(),
-                                          sk.data_ptr(), due.data_ptr(), cap, C.byref(n), _flow_stream(keys_a)),
-          "flows_merge")
-    return keys[:n.value], sk[:n.value], due[:n.value]
+    n = _flows_merge_into(ctx, keys_a, sk_a, na, keys_b, sk_b, nb, t, frequency_pkts, keys, sk, due)
+    return keys[:n], sk[:n], due[:n]
 
 
 def flows_diff(keys_a, sk_a, keys_b, sk_b, ctx: Context | None = None):
@@ -1136,13 +963,13 @@ def flows_diff(keys_a, sk_a, keys_b, sk_b, ctx: Context | None = None):
     n_matched): diffs is the CUDA int32 record tensor [na, 4 + t] in a's key
     order — a[i] minus its b record where the key is in b, a[i] itself
     otherwise — which decode_segments accepts unchanged."""
-    import torch
-    ctx = _flow_ctx(ctx, keys_a, keys_b)
+    ctx = _context(ctx, keys_a, keys_b)
     na, nb, t = _flow_pair(keys_a, sk_a, keys_b, sk_b)
+    torch = need_torch()
     out = torch.empty((na, 4 + t), dtype=torch.int32, device=keys_a.device)
     m = C.c_size_t()
     check(lib().qk_u32_flows_diff_device(ctx.handle, keys_a.data_ptr(), sk_a.data_ptr(), na, keys_b.data_ptr(),
-                                         sk_b.data_ptr(), nb, t, out.data_ptr(), C.byref(m), _flow_stream(keys_a)),
+                                         sk_b.data_ptr(), nb, t, out.data_ptr(), C.byref(m), stream_of(keys_a)),
           "flows_diff")
     return out, m.value
 
@@ -1152,7 +979,7 @@ def flows_lookup(keys, sk, query, ctx: Context | None = None) -> list:
     12-byte AddrKeys against a flow array (qk_u32_flows_lookup_device): one
     PowerSumQuackU32 per queried key, None where the table has no such flow.
     Any order, repeats allowed."""
-    ctx = _flow_ctx(ctx, keys)
+    ctx = _context(ctx, keys)
     n, t = _flow_array(keys, sk, "table")
     query = [bytes(k) for k in query]
     if any(len(k) != 12 for k in query):
@@ -1165,9 +992,9 @@ def flows_lookup(keys, sk, query, ctx: Context | None = None) -> list:
     out = C.create_string_buffer(nk * rec)
     found = C.create_string_buffer(nk)
     check(lib().qk_u32_flows_lookup_device(ctx.handle, keys.data_ptr(), sk.data_ptr(), n, t, hk, nk, out, found,
-                                           _flow_stream(keys)), "flows_lookup")
+                                           stream_of(keys)), "flows_lookup")
     raw, f = out.raw, found.raw
-    return [_quack_from_bytes(raw[i * rec:(i + 1) * rec], t) if f[i] else None for i in range(nk)]
+    return [PowerSumQuackU32._from_record(raw[i * rec:(i + 1) * rec], t) if f[i] else None for i in range(nk)]
 
 
 def wire_max(threshold: int) -> int:
@@ -1188,12 +1015,10 @@ def emit_wire(keys, sketches, select=None, stride: int | None = None, ctx: Conte
     (or None), int32 [m] row indices, uint8 [m, stride] images, int32 [m]
     image lengths.  Image r is wire[r, :lens[r]], byte-equal to
     sketches[rows[r]].serialize()."""
-    import torch
-    ctx = _flow_ctx(ctx, sketches, keys)
+    ctx = _context(ctx, sketches, keys)
+    torch = need_torch()
     if keys is None:
-        ok = (isinstance(sketches, torch.Tensor) and sketches.is_cuda and sketches.dtype == torch.int32
-              and sketches.dim() == 2 and sketches.shape[1] > 4 and sketches.is_contiguous())
-        if not ok:
+        if not is_record_tensor(sketches):
             raise TypeError("sketches must be a contiguous CUDA int32 [n, 4 + t] record tensor")
         n, t = sketches.shape[0], sketches.shape[1] - 4
     else:
@@ -1215,7 +1040,7 @@ def emit_wire(keys, sketches, select=None, stride: int | None = None, ctx: Conte
         ctx.handle, keys.data_ptr() if keys is not None and n else None, sketches.data_ptr() if n else None, n, t,
         select.data_ptr() if select is not None and n else None, stride,
         keys_out.data_ptr() if keys_out is not None and n else None, rows.data_ptr() if n else None,
-        wire.data_ptr() if n else None, lens.data_ptr() if n else None, n, C.byref(m), _flow_stream(sketches)),
+        wire.data_ptr() if n else None, lens.data_ptr() if n else None, n, C.byref(m), stream_of(sketches)),
         "emit_wire")
     m = m.value
     return (keys_out[:m] if keys_out is not None else None), rows[:m], wire[:m], lens[:m]
@@ -1233,23 +1058,21 @@ def ingest_wire(wire, lens, flow, nflows: int, threshold: int, peer=None, ctx: C
     sender_step takes them — and `status` a host int32 array: QK_OK for a
     winner, QK_WIRE_SUPERSEDED for an accepted image a later one of the same
     flow replaced, else what deserialize returns for it."""
-    import torch
-    ctx = _flow_ctx(ctx, wire, peer)
+    ctx = _context(ctx, wire, peer)
+    torch = need_torch()
     nflows, t = int(nflows), int(threshold)
     if not (isinstance(wire, torch.Tensor) and wire.is_cuda and wire.dtype == torch.uint8 and wire.dim() == 2
             and wire.is_contiguous()):
         raise TypeError("wire must be a contiguous CUDA uint8 tensor [n, stride]")
     n, stride = wire.shape
     device = wire.device
-    if _u32_len(lens, "lens") != n or _u32_len(flow, "flow") != n:
+    if uint_len(lens, "lens") != n or uint_len(flow, "flow") != n:
         raise ValueError("lens and flow must hold one entry per datagram")
-    lens = _u32_on_device(lens, device, "lens")
-    flow = _u32_on_device(flow, device, "flow")
+    lens = uint_on_device(lens, device, "lens")
+    flow = uint_on_device(flow, device, "flow")
     if peer is None:
-        fresh = torch.from_numpy(np.frombuffer(PowerSumQuackU32(t)._buf, dtype=np.int32).copy()).to(device)
-        peer = fresh.unsqueeze(0).expand(nflows, -1).contiguous()
-    elif not (isinstance(peer, torch.Tensor) and peer.is_cuda and peer.dtype == torch.int32 and peer.is_contiguous()
-              and tuple(peer.shape) == (nflows, 4 + t) and peer.device == device):
+        peer = _fresh_record(t, device).unsqueeze(0).expand(nflows, -1).contiguous()
+    elif not (is_record_tensor(peer, 0) and tuple(peer.shape) == (nflows, 4 + t) and peer.device == device):
         raise TypeError("peer must be a contiguous CUDA int32 record tensor [nflows, 4 + t] on wire's device")
     present = torch.empty((nflows,), dtype=torch.uint8, device=device)
     status = np.zeros(max(n, 1), dtype=np.int32)
@@ -1257,8 +1080,7 @@ def ingest_wire(wire, lens, flow, nflows: int, threshold: int, peer=None, ctx: C
     check(lib().qk_u32_wire_ingest_device(
         ctx.handle, wire.data_ptr() if n else None, max(int(stride), 1), lens.data_ptr() if n else None,
         flow.data_ptr() if n else None, n, t, nflows, peer.data_ptr() if nflows else None,
-        present.data_ptr() if nflows else None, status.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(acc),
-        _flow_stream(wire)), "ingest_wire")
+        present.data_ptr() if nflows else None, ptr(status), C.byref(acc), stream_of(wire)), "ingest_wire")
     return peer, present, status[:n], acc.value
 
 
@@ -1282,7 +1104,7 @@ class DeviceFlowQuacks:
         return self._n
 
     def _empty(self):
-        import torch
+        torch = need_torch()
         dev = f"cuda:{self.device}"
         return (torch.empty((0, 12), dtype=torch.uint8, device=dev),
                 torch.empty((0, 4 + self.threshold), dtype=torch.int32, device=dev))
@@ -1302,7 +1124,6 @@ class DeviceFlowQuacks:
     def merge(self, keys, sketches, frequency_pkts: int = 0, ctx: Context | None = None):
         """Merge a flow array (the later stream) into the table; returns the
         `due` flags of the new table (a view, valid until the next update)."""
-        import torch
         ctx = ctx or get_context(self.device)
         nb, t = _flow_array(keys, sketches, "batch")
         if t != self.threshold:
@@ -1311,18 +1132,14 @@ class DeviceFlowQuacks:
         need, o = self._n + nb, 1 - self._cur
         if self._bufs[o] is None or self._bufs[o][0].shape[0] < need:
             rows = max(need, 1024, 2 * (self._bufs[o][0].shape[0] if self._bufs[o] is not None else 0))
-            dev = f"cuda:{self.device}"
+            torch, dev = need_torch(), f"cuda:{self.device}"
             self._bufs[o] = (torch.empty((rows, 12), dtype=torch.uint8, device=dev),
                              torch.empty((rows, 4 + t), dtype=torch.int32, device=dev),
                              torch.empty((rows,), dtype=torch.uint8, device=dev))
         ko, so, do = self._bufs[o]
-        n = C.c_size_t()
-        check(lib().qk_u32_flows_merge_device(ctx.handle, ka.data_ptr(), sa.data_ptr(), self._n, keys.data_ptr(),
-                                              sketches.data_ptr(), nb, t, int(frequency_pkts), ko.data_ptr(),
-                                              so.data_ptr(), do.data_ptr(), ko.shape[0], C.byref(n),
-                                              _flow_stream(ko)), "flows_merge")
-        self._cur, self._n = o, n.value
-        return do[:self._n]
+        n = _flows_merge_into(ctx, ka, sa, self._n, keys, sketches, nb, t, frequency_pkts, ko, so, do)
+        self._cur, self._n = o, n
+        return do[:n]
 
     def emit(self, select=None, stride: int | None = None, ctx: Context | None = None):
         """The wire images of the selected flows of the table (emit_wire):
@@ -1371,9 +1188,8 @@ class DeviceFlowQuacks:
             return {}
         k = self.keys.cpu().numpy()
         raw = self.sketches.cpu().numpy().tobytes()
-        rec = 4 * (4 + self.threshold)
-        return {k[i].tobytes(): _quack_from_bytes(raw[i * rec:(i + 1) * rec], self.threshold)
-                for i in range(self._n)}
+        quacks = _quacks_from_records(raw, 4 * (4 + self.threshold), self._n, self.threshold)
+        return {k[i].tobytes(): q for i, q in enumerate(quacks)}
 
     def diff(self, peer, ctx: Context | None = None):
         """media_client.rs:295-296 per flow: this table minus `peer` (another
@@ -1391,21 +1207,18 @@ def partial_words(threshold: int, bits: int = 32) -> int:
 def encode_device_async(ctx: Context, ids, threshold: int, partial, bits: int = 32, stream=None) -> None:
     """Enqueue encode of a CUDA id tensor into a CUDA int64 `partial` tensor
     of partial_words(threshold, bits) words (layout: include/quack_hip.h)."""
-    ptr, n, _, s = _device_array(ids, bits)
-    if stream is None:
-        stream = s
-    check(getattr(lib(), f"qk_u{bits}_encode_device_async")(ctx.handle, ptr, n, threshold,
-                                                              partial.data_ptr(), stream), "encode_device_async")
+    iptr, n, _, s = _device_array(ids, bits)
+    check(getattr(lib(), f"qk_u{bits}_encode_device_async")(
+        ctx.handle, iptr, n, threshold, partial.data_ptr(), s if stream is None else stream), "encode_device_async")
 
 
 def merge_partial(q: _PowerSumQuack, partial_host, has_last: bool, last: int) -> None:
     arr = np.ascontiguousarray(np.asarray(partial_host).astype(np.uint64))
-    check(q._f("merge_partial")(q._buf, arr.ctypes.data_as(C.POINTER(C.c_uint64)), int(has_last), int(last)),
-          "merge_partial")
+    check(q._f("merge_partial")(q._buf, ptr(arr), int(has_last), int(last)), "merge_partial")
 
 
 def fill_splitmix(ctx: Context, out, seed: int, start: int = 0, bits: int = 32, stream=None) -> None:
     """Fill a CUDA tensor with the synthetic splitmix64 id stream (device-side)."""
-    ptr, n, _, s = _device_array(out, bits)
-    check(getattr(lib(), f"qk_fill_splitmix_u{bits}")(ctx.handle, ptr, n, seed & 0xFFFFFFFFFFFFFFFF, start,
+    optr, n, _, s = _device_array(out, bits)
+    check(getattr(lib(), f"qk_fill_splitmix_u{bits}")(ctx.handle, optr, n, seed & 0xFFFFFFFFFFFFFFFF, start,
                                                         s if stream is None else stream), "fill_splitmix")

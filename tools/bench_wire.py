@@ -12,7 +12,7 @@ warmed, the arms alternated; one JSON line per selection (median, min, max of
   host_emit    what the proxy could do before: flows_lookup of the selected
                keys (one PowerSumQuackU32 per flow), .serialize() per flow
   host_ingest  what the sender could do before: PowerSumQuackU32.deserialize
-               per datagram, then the record tensor uploaded (_record_tensor)
+               per datagram, then the record tensor uploaded (Records.to_device)
   copy         the yardstick: torch copy, device to device, of the image bytes
 
     python tools/bench_wire.py [--flows 100000] [--t 32] [--select 0.1 1.0] [--rounds 10]
@@ -52,7 +52,8 @@ def make_table(torch, n, t, seed):
 
 
 def run(torch, sk, lib, ctx, a, frac):
-    from sidekick_amd.quack import _record_tensor, flows_lookup
+    from sidekick_amd._args import Records
+    from sidekick_amd.quack import flows_lookup
     n, t = a.flows, a.t
     stride = sk.wire_max(t)
     keys, recs, d_keys, d_recs = make_table(torch, n, t, 7)
@@ -96,7 +97,7 @@ def run(torch, sk, lib, ctx, a, frac):
 
     def host_ingest():
         quacks = [sk.PowerSumQuackU32.deserialize(b) for b in state["images"]]
-        state["peer"] = _record_tensor(quacks, "peer", [ctx], ctx)[0]
+        state["peer"] = Records.parse(quacks, sk.PowerSumQuackU32).to_device(ctx, "peer")
 
     def copy():
         copy_dst.copy_(wire)
