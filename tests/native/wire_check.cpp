@@ -8,6 +8,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <set>
 #include <string>
 #include <vector>
 
@@ -104,8 +105,18 @@ static void validator_table(uint32_t T) {
     add("threshold 2^32 + t", pack((1ull << 32) + T, ok, 1, 5, 6, true), QK_E_FORMAT);
     add("threshold 2^63", pack(1ull << 63, ok, 1, 5, 6, true), QK_E_FORMAT);
     add("threshold 2^62 - 2 (4t wraps in 64 bits)", pack((1ull << 62) - 2, ok, 1, 5, 6, true), QK_E_FORMAT);
-    for (uint32_t at : {0u, T - 1}) {
-        std::vector<uint32_t> s = ok;
+    // one sum out of range, the others p - 1 or ordinary: the first and last of a 64-lane share's first,
+    // second and third trips, and the image's last two
+    std::set<uint32_t> bad_at;
+    for (uint32_t at : {0u, 1u, 62u, 63u, 64u, 65u, 126u, 127u, 128u, 129u, T - 2, T - 1})
+        if (at < T) bad_at.insert(at);
+    for (uint32_t at : bad_at) {
+        std::vector<uint32_t> s = top;
+        s[at] = QK_P32;
+        add("sums p - 1 but one equal to p", pack(T, s, at & 1, 5, 6, at & 1), QK_E_FORMAT);
+        s[at] = 0xFFFFFFFFu;
+        add("sums p - 1 but one equal to 2^32 - 1", pack(T, s, ~at & 1, 5, 6, ~at & 1), QK_E_FORMAT);
+        s = ok;
         s[at] = QK_P32;
         add("a sum equal to p", pack(T, s, 1, 5, 6, true), QK_E_FORMAT);
         s[at] = 0xFFFFFFFFu;
@@ -146,8 +157,9 @@ static void image_of_record(uint32_t T, int has_last, uint32_t count, uint32_t f
 }
 
 int main() {
-    for (uint32_t T : {1u, 2u, 7u, 32u, 1024u}) validator_table(T);   // t = 1: threshold 0 is an image of its own
-    for (uint32_t T : {1u, 2u, 7u, 32u, 1024u})
+    // t = 1: threshold 0 is an image of its own; 64, 65, 129: a 64-lane share of one, two and three trips
+    for (uint32_t T : {1u, 2u, 7u, 32u, 64u, 65u, 129u, 1024u}) validator_table(T);
+    for (uint32_t T : {1u, 2u, 7u, 32u, 64u, 65u, 129u, 1024u})
         for (int has_last = 0; has_last < 2; ++has_last) {
             image_of_record(T, has_last, 0, 0);
             image_of_record(T, has_last, 0xFFFFFFFFu, QK_P32 - 1);
