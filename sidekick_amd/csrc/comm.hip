@@ -65,6 +65,7 @@
 #include <chrono>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 #include <rccl/rccl.h>
 #include <vector>
 
@@ -387,7 +388,8 @@ static int encode_sharded_async(qk_comm *c, const void *const *d_ids, const size
     if (t == 0 || t > QK_MAX_THRESHOLD) return QK_E_THRESHOLD;
     if (root < 0 || root >= c->world) return QK_E_INVAL;
     c->step = 0;
-    const size_t esz = BITS == 32 ? 4 : 8;
+    using T = typename std::conditional<BITS == 32, uint32_t, uint64_t>::type;
+    const size_t esz = sizeof(T);
     const size_t R = reduce_words(BITS, t), W = R + 2 * (size_t)c->world + 1;
     // per-rank arguments and local work: a failure still joins the reduce,
     // with the failed payload
@@ -405,8 +407,7 @@ static int encode_sharded_async(qk_comm *c, const void *const *d_ids, const size
         if (!e) e = enter(L);
         if (!e) {
             std::lock_guard<std::mutex> g(L.ctx->mu);
-            e = BITS == 32 ? launch_encode_u32(L.ctx, (const uint32_t *)d_ids[i], n[i], t, L.d_coll, L.ctx->stream)
-                           : launch_encode_u64(L.ctx, (const uint64_t *)d_ids[i], n[i], t, L.d_coll, L.ctx->stream);
+            e = Width<T>::launch_encode(L.ctx, (const T *)d_ids[i], n[i], t, L.d_coll, L.ctx->stream);
         }
         if (!e) {
             hipLaunchKernelGGL(k_comm_pack, dim3(1), dim3(64), 0, L.ctx->stream, L.d_coll, (uint32_t)R,
@@ -465,8 +466,8 @@ static int encode_sharded_wait(qk_comm *c, Q *q) {
                 last = h[R + 2 * r + 1];
                 break;
             }
-        if constexpr (BITS == 32) return qk_u32_merge_partial(q, h, has, (uint32_t)last);
-        else return qk_u64_merge_partial(q, h, has, last);
+        using T = typename std::conditional<BITS == 32, uint32_t, uint64_t>::type;
+        return Width<T>::merge_partial(q, h, has, (T)last);
     }
     return QK_OK;   // not the root: q is untouched
 }
@@ -515,8 +516,7 @@ static int decode_sharded(qk_comm *c, const Q *diff, int root, const T *const *d
         if (!status && !diff) status = QK_E_INVAL;
         if (!status && diff->count != 0) {
             std::vector<T> cf(std::max<uint32_t>(diff->threshold, 1));
-            if constexpr (sizeof(T) == 4) status = qk_u32_to_coeffs(diff, cf.data(), (uint32_t)cf.size(), &d);
-            else status = qk_u64_to_coeffs(diff, cf.data(), (uint32_t)cf.size(), &d);
+            status = Width<T>::to_coeffs(diff, cf.data(), (uint32_t)cf.size(), &d);
             if (status == QK_OK && d > QK_MAX_THRESHOLD) status = QK_E_THRESHOLD;
             if (status == QK_OK)
                 for (uint32_t k = 0; k < d; ++k) h[4 + k] = (uint64_t)cf[k];

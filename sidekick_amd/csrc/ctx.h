@@ -8,6 +8,7 @@
 
 #include "argcheck.h"
 #include "quack_hip.h"
+#include "rootset.h"
 
 // Per-context knobs (qk_ctx_set_knob).  Round 6 removed every knob that
 // selected a measured-and-rejected variant ("measured and
@@ -28,15 +29,37 @@ struct qk_knobs {
                            // (profiles/r05/flows_hist/)
     int flow_byslot = 0;   // per-flow grouping-sort key: 0 the pass-count rule (flows.hip), 1 force by slot,
                            // 2 force by flow rank (tests cover both product paths)
-    int root_test = 0;     // 0: automatic (cost model, api.hip rt_use_scan), 1: Horner, 2: root-set scan
+    int root_test = 0;     // 0: automatic (cost model, decode.hip rt_use_scan), 1: Horner, 2: root-set scan
     int comm_fault = 0;    // k > 0 (tests): this rank's payload staging for the k-th collective of its
                            // next sharded operation fails, once (comm.hip fault_now)
-    int rt_karg = 1;       // 1: a root-set scan whose set fits the kernel arguments takes them (api.hip
+    int rt_karg = 1;       // 1: a root-set scan whose set fits the kernel arguments takes them (decode.hip
                            // root_test_scan_k; configs[4] u64 wall 172 -> 167 us, u32 even,
                            // profiles/r06/s6_karg_s1/); 0: always the set by an H2D copy (the path of
                            // larger sets and of the sharded decode; tests compare the two)
     int comm_delay_ms = 0; // k > 0 (tests): a k-ms kernel in front of this rank's next RCCL collective,
                            // once (comm.hip mark_pre: the bounded wait for pre-collective work)
+};
+
+// Running state of the kernel-argument root-set scan (decode.hip
+// root_test_scan_k), which resets nothing in front of its kernel.  Invariant:
+// `valid`: the device tickets (d_small[SMALL_KT], [SMALL_KT + 3]) equal hbase /
+// sbase; `slots_clean`: every pinned slot holds ~0, the overflow flag 0.  The
+// copy form counts in words of its own: it dirties the slots and leaves the
+// tickets alone.  A failed launch or a slot overflow loses the tickets; one
+// memset before the next kernel-argument call resets them.
+struct qk_rt_karg {
+    uint64_t hbase = 0, sbase = 0;
+    bool valid = false, slots_clean = false;
+    uint64_t gen = 0;      // the completion mark's last value (the host polls that word); each call takes the next
+    int occ[2] = {0, 0};   // k_root_scan_k<u32 / u64, 1> workgroups per CU (0: not yet asked)
+
+    void slots_written() { slots_clean = false; }   // by the copy form, or by a call in flight
+    void tickets_lost() { valid = false; }
+    void tickets_reset() { hbase = sbase = 0, valid = true; }   // with the memset of d_small[SMALL_KT ..+4)
+    void call_done(const qk::RtSlotRead &r) {       // a clean call, its slots restored
+        hbase += r.hits, sbase += r.stops;
+        slots_clean = true;
+    }
 };
 
 struct qk_ctx {
@@ -56,18 +79,7 @@ struct qk_ctx {
     uint64_t *d_small = nullptr;       // partial output / hit counters (small, fixed)
     uint64_t *h_small = nullptr;       // pinned mirror of d_small
     uint64_t *h_small_dev = nullptr;   // h_small as the device addresses it
-    // the kernel-argument root-set scan keeps its hit / stop tickets
-    // (d_small[0], [3]) running across calls: their values now, when valid
-    uint64_t rt_hbase = 0, rt_sbase = 0;
-    bool rt_bases_valid = false;
-    // the pinned hit / stop slots hold ~0 everywhere (the kernel-argument
-    // scan restores the few it used instead of re-filling all 1020 words)
-    bool rt_slots_clean = false;
-    // k_root_scan_k<u32 / u64, 1> workgroups per CU (0: not yet asked)
-    int rt_occ_k[2] = {0, 0};
-    // the value the next kernel-argument scan's last workgroup writes to
-    // h_small[SMALL_DONE] (the host polls that word, not the stream)
-    uint64_t rt_gen = 0;
+    qk_rt_karg rt;                     // the kernel-argument root-set scan's running state
     uint64_t *d_hits = nullptr;
     size_t hits_cap = 0;
     // the dynamic encode's chunk counters (d_small[ENC_CLAIM + k * stride])
@@ -132,26 +144,7 @@ struct qk_ctx {
 
 namespace qk {
 
-// Small-buffer layout (u64 words).  Root tests: d_small[0] hit count, [1]
-// first stop, [3] stops recorded (root-set scan), [RT_C ..) the
-// coefficients or the root set — one H2D copy of h_small[0 .. RT_C + words)
-// sets all of it.  Results in h_small from SMALL_NHITS: count, stop, the
-// overflow flag of the direct form, then from SMALL_HITPF the first hits and
-// at the end RT_NSTOP stop slots.  Horner's arrive by D2H copies; the
-// root-set scan writes its hits and stops there itself (decode.hip
-// rt_record) and the host derives count and stop from the slots.
-constexpr size_t SMALL_WORDS = 4096;   // >= max partial words (2*1024+2) plus counters
-constexpr size_t RT_C = 4;             // root tests: coefficients / root set from d_small[RT_C]
-constexpr size_t SMALL_NHITS = 3072;   // h_small: hit count
-constexpr size_t SMALL_STOP = 3073;    // h_small: first stop index
-constexpr size_t SMALL_OVF = 3074;     // h_small: a hit or stop slot past the direct form's room
-constexpr size_t SMALL_DONE = 3075;    // h_small: the kernel-argument scan's completion mark
-constexpr size_t SMALL_HITPF = 3076;   // h_small: the first hits
-constexpr uint32_t RT_NSTOP = 16;      // stop slots of the direct form
-constexpr size_t SMALL_STOPS = SMALL_WORDS - RT_NSTOP;
-constexpr size_t SMALL_HITPF_N = SMALL_STOPS - SMALL_HITPF;
-// the same slots relative to SMALL_NHITS (the kernel's hout)
-constexpr size_t RT_STOP0 = SMALL_STOPS - SMALL_NHITS;
+// Small-buffer layout: rootset.h; the device-only words follow.
 // d_small[SMALL_KT ..+4): the kernel-argument root-set scan's counters (hit
 // ticket, stop minimum, -, stop ticket), apart from everything else that
 // writes d_small (encode partials, the two-phase root test's header)
@@ -205,7 +198,7 @@ int scratch_release(qk_ctx *ctx, hipStream_t s);
 // grow-only buffers; growth never synchronises the device (the old buffer is
 // retired, api.hip regrow)
 int ensure_scratch(qk_ctx *ctx, size_t bytes, hipStream_t s);
-int ensure_hits(qk_ctx *ctx, size_t cap, hipStream_t s);
+int ensure_hits(qk_ctx *ctx, size_t cap);
 int ensure_flow(qk_ctx *ctx, int which, size_t bytes, hipStream_t s);
 int ensure_stage(qk_ctx *ctx, size_t bytes);
 int ensure_items(qk_ctx *ctx, size_t bytes);
@@ -230,51 +223,22 @@ int launch_encode_u32_acc(qk_ctx *ctx, const uint32_t *d_ids, size_t n, uint32_t
 int launch_encode_u64_acc(qk_ctx *ctx, const uint64_t *d_ids, size_t n, uint32_t t,
                           uint64_t *d_partial, hipStream_t s);
 
-int launch_root_test_u32(qk_ctx *ctx, const uint32_t *d_c, uint32_t d, const uint32_t *log, size_t n,
-                         int use_stop, uint32_t stop_value, uint64_t *hits, uint64_t cap, uint64_t *counters,
-                         hipStream_t s);
 // canonical power sums out[0..T) from per-block partials [power][block] (encode.hip)
 int launch_finalize_powers_u32(const uint64_t *partials, uint32_t nblocks, uint32_t T, uint64_t *out,
                                hipStream_t s);
-// u64 root test by baby-step/giant-step for these degrees (decode.hip); the
-// coefficient buffer then holds rt64_bsgs_table's limb-shifted table
-bool rt64_use_bsgs(const qk_ctx *ctx, uint32_t d);
 // largest degree the root-set scan takes (its set must fit d_small)
 constexpr uint32_t RT_SCAN_MAXD = 256;
-size_t rt64_bsgs_table(const uint64_t *coeffs, uint32_t d, uint64_t *out);
-int launch_root_test_u64(qk_ctx *ctx, const uint64_t *d_c, uint32_t d, const uint64_t *log, size_t n,
-                         int use_stop, uint64_t stop_value, uint64_t *hits, uint64_t cap, uint64_t *counters,
-                         hipStream_t s);
 
-// root-set scan (decode.hip): the hash set of P's roots in LDS
-struct RtScanSet {
-    uint32_t S = 1, words = 0, m1 = 1, m2 = 1, shift = 28;
-};
-template <typename T>
-bool rt_scan_table(const T *roots, uint32_t k, RtScanSet &set, std::vector<T> &out, bool compact = false);
-// the root-set scan with its set in the kernel arguments (decode.hip)
-constexpr size_t RT_KTAB_BYTES = 2048;
-struct RtKTab {
-    uint64_t w[RT_KTAB_BYTES / 8];
-};
-template <typename T>
-int launch_root_scan_k(qk_ctx *ctx, const std::vector<T> &tab, const RtScanSet &set, const T *log, size_t n,
-                       int use_stop, T stop_value, uint64_t *hits, uint64_t cap, uint64_t *counters, uint64_t *hout,
-                       uint64_t hbase, uint64_t sbase, uint64_t *done, uint64_t gen, hipStream_t s);
-template <typename T>
-int launch_root_scan(qk_ctx *ctx, const T *d_tab, const RtScanSet &set, const T *log, size_t n, int use_stop,
-                     T stop_value, uint64_t *hits, uint64_t cap, uint64_t *counters, uint64_t *hout,
-                     hipStream_t s);
-
-// root test in two phases (api.hip): root_test_plan picks Horner or the
-// root-set scan for (d, n) and, for the scan, finds the roots on the host and
-// builds the set (once per call, shared by every shard of a sharded decode);
-// root_test_begin enqueues on s; root_test_finish waits and collects the
-// sorted hit positions (all of them) and the first stop position
+// root test in two phases (decode.hip), so that several devices (comm.hip)
+// have theirs in flight at once: root_test_plan picks Horner or the root-set
+// scan for (d, n) and, for the scan, finds the roots and builds the set (once
+// per call, shared by every shard); root_test_begin enqueues on s;
+// root_test_finish collects the sorted hit positions and the first stop
 template <typename T> struct RtPlan {
-    bool scan = false;    // the root-set scan, writing its hits into pinned host slots (else Horner)
-    RtScanSet set;
-    std::vector<T> tab;   // the root set (scan)
+    bool scan = false;       // the root-set scan, writing its hits into pinned host slots (else Horner)
+    std::vector<T> roots;    // P's distinct roots, found once (scan)
+    RtScanSet set, kset;     // the set of the copy form; the compact set of the kernel arguments
+    std::vector<T> tab, ktab;   // each built from roots when its form runs (words == 0: not built)
 };
 template <typename T> int root_test_plan(const qk_ctx *ctx, const T *coeffs, uint32_t d, size_t n, RtPlan<T> &plan);
 template <typename T>
@@ -283,5 +247,26 @@ int root_test_begin(qk_ctx *ctx, const RtPlan<T> &plan, const T *coeffs, uint32_
 template <typename T>
 int root_test_finish(qk_ctx *ctx, const RtPlan<T> &plan, const T *coeffs, uint32_t d, const T *d_log, size_t n,
                      int use_stop, T stop_value, hipStream_t s, std::vector<uint64_t> &hits, uint64_t &stop_index);
+
+// the two id widths behind one template: the quACK type and its typed functions
+template <typename T> struct Width;
+template <> struct Width<uint32_t> {
+    using quack = qk_u32;
+    static constexpr auto *launch_encode = &launch_encode_u32, *launch_encode_acc = &launch_encode_u32_acc;
+    static constexpr auto *partial_words = &qk_u32_partial_words;
+    static constexpr auto *merge_partial = &qk_u32_merge_partial;
+    static constexpr auto *to_coeffs = &qk_u32_to_coeffs;
+    static constexpr auto *roots = &qk_u32_roots;
+    static constexpr size_t last_word(uint32_t t) { return (size_t)t + 1; }   // of a partial: the last id
+};
+template <> struct Width<uint64_t> {
+    using quack = qk_u64;
+    static constexpr auto *launch_encode = &launch_encode_u64, *launch_encode_acc = &launch_encode_u64_acc;
+    static constexpr auto *partial_words = &qk_u64_partial_words;
+    static constexpr auto *merge_partial = &qk_u64_merge_partial;
+    static constexpr auto *to_coeffs = &qk_u64_to_coeffs;
+    static constexpr auto *roots = &qk_u64_roots;
+    static constexpr size_t last_word(uint32_t t) { return 2 * (size_t)t + 1; }
+};
 
 } // namespace qk

@@ -13,9 +13,11 @@
 // atomic ticket; the host sorts them into log order.  The `break` at the
 // first log entry equal to diff.last_value() becomes an atomicMin of that
 // position; the host drops hits at or after it.
+// Kernels, launchers, the host driver, the C entry points; its pure host logic is rootset.h.
 #include <algorithm>
-#include <cstdlib>
+#include <chrono>
 #include <cstring>
+#include <thread>
 #include <type_traits>
 #include <vector>
 
@@ -29,10 +31,12 @@ QK_WARM_KERNEL(decode)
 
 constexpr int RT_BLOCK = 256;
 
-// hout (optional, k_root_scan): the hit / stop also into pinned host memory.
+// hout (optional, k_root_scan): the hit / stop also into pinned host memory
+// (the slots of rootset.h RtSlots, from its result()).
 // hbase / sbase: the values the hit / stop tickets (counters[0], [3]) start
-// from in this launch (0 after the host reset them; the kernel-argument form
-// of the scan keeps them running across calls instead of resetting them)
+// from in this launch (0 after the host reset them, root_test_begin; the
+// kernel-argument form of the scan, root_test_scan_k below, keeps them
+// running across calls instead of resetting them: ctx.h qk_rt_karg)
 __device__ __forceinline__ void rt_record(uint64_t pos, bool hit, bool stop, uint64_t *hits, uint64_t cap,
                                           uint64_t *counters, uint64_t *hout = nullptr, uint32_t nhpf = 0,
                                           uint64_t hbase = 0, uint64_t sbase = 0) {
@@ -210,7 +214,7 @@ __global__ __launch_bounds__(RT_BLOCK) void k_root_test_u64(const uint64_t *__re
 // p_(8a+b) * 2^(22j) mod p (u64), blocks a = 0 .. nblk - 1 (the last one the
 // top block when d % 8 != 0).
 constexpr uint32_t RT64_BSGS_MIND = 16;
-constexpr uint32_t RT64_BSGS_MAXD = 1000;   // (ceil((d+1)/8) * 24 words <= SMALL_NHITS - RT_C)
+constexpr uint32_t RT64_BSGS_MAXD = 1000;   // (ceil((d+1)/8) * 24 words * 8 <= RT_SET_BYTES)
 
 __device__ __forceinline__ uint64_t rt_limb_sum(uint64_t lo, uint64_t hi, uint64_t c) {
     // lo + hi * 2^32 + c  (lo, hi < 2^59) reduced below 2^64 (not canonical)
@@ -359,41 +363,8 @@ __global__ __launch_bounds__(RT_BLOCK) void k_root_test_u64_bsgs(const uint64_t 
     }
 }
 
-bool rt64_use_bsgs(const qk_ctx *ctx, uint32_t d) {
-    (void)ctx;
-    return d >= RT64_BSGS_MIND && d <= RT64_BSGS_MAXD;
-}
-
-// host: the limb-shifted coefficient table of the BSGS kernel into out[]
-// (canonical c_1..c_d of the monic polynomial); returns the words written
-size_t rt64_bsgs_table(const uint64_t *coeffs, uint32_t d, uint64_t *out) {
-    const uint32_t nfull = d / 8, r = d % 8, nblk = nfull + (r ? 1 : 0);
-    const size_t words = (size_t)nblk * 24;
-    for (size_t i = 0; i < words; ++i) out[i] = 0;
-    for (uint32_t k = 0; k < 8 * nblk; ++k) {
-        uint64_t pk;   // coefficient of x^k: p_d = 1, p_(d-i) = c_i
-        if (k > d) pk = 0;
-        else if (k == d) pk = 1;
-        else pk = coeffs[d - k - 1];
-        unsigned __int128 v = pk;
-        for (int j = 0; j < 3; ++j) {
-            out[(size_t)k * 3 + j] = (uint64_t)(v % P64);
-            v = (v % P64) << 22;
-        }
-    }
-    return words;
-}
-
-template <typename KernelT>
-static uint32_t rs_grid(qk_ctx *ctx, KernelT kern, uint64_t units, size_t lds) {
-    if (ctx->grid_override) return ctx->grid_override;
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, RT_BLOCK, lds) != hipSuccess || occ < 1) occ = 1;
-    const uint64_t full = (uint64_t)ctx->num_cus * occ;
-    uint64_t need = (units + RT_BLOCK - 1) / RT_BLOCK;
-    if (need < 1) need = 1;
-    return (uint32_t)(need < full ? need : full);
-}
+// (the coefficient buffer then holds rootset.h rt64_bsgs_table's limb-shifted table)
+static bool rt64_use_bsgs(uint32_t d) { return d >= RT64_BSGS_MIND && d <= RT64_BSGS_MAXD; }
 
 // ------------------------------------------------------- root-set scan
 // The same hit list from the roots of P (roots.cpp): P(x) == 0 exactly when
@@ -417,16 +388,14 @@ template <> __device__ __forceinline__ uint64_t rs_reduce<uint64_t>(uint64_t x) 
 template <typename T, int S>
 __device__ __forceinline__ bool rs_member(T x, const T *__restrict__ set, uint32_t m1, uint32_t m2, uint32_t shift) {
     const T xr = rs_reduce<T>(x);
-    uint32_t hh = (uint32_t)xr * m1;
-    if constexpr (sizeof(T) == 8) hh += (uint32_t)(xr >> 32) * m2;
-    const T *b = set + (size_t)(hh >> shift) * S;
+    const T *b = set + (size_t)(rs_hash<T>(xr, m1, m2) >> shift) * S;
     bool hit = false;
 #pragma unroll
     for (int j = 0; j < S; ++j) hit |= b[j] == xr;
     return hit;
 }
 
-// hout (pinned host memory, the context's h_small from SMALL_NHITS): every
+// hout (pinned host memory, the context's h_small from RtSlots::result()): every
 // recorded hit also goes straight to the host — hit slot k < nhpf to
 // hout[4 + k], a stop to one of the RT_NSTOP stop slots (device counter
 // counters[3]) — and a slot past either sets the overflow flag hout[2], so
@@ -504,9 +473,12 @@ __global__ __launch_bounds__(RT_BLOCK) void k_root_scan(const T *__restrict__ lo
 // its hits and stops written, takes a ticket of its group (workgroup index
 // mod G, G = min(grid, RT_DONE_GROUPS), done[16 g]); the last of a group
 // takes a ticket of the groups (done[16 G_max]), and the last of those
-// writes gen to hout[SMALL_DONE - SMALL_NHITS], the word the host polls — it
+// writes gen to hout[RT_DONE0], the completion mark the host polls — it
 // sees the result without waiting for the end-of-kernel signal.  Each last
 // taker resets its ticket for the next launch.
+struct RtKTab {
+    uint64_t w[RT_KTAB_BYTES / 8];
+};
 template <typename T, int S>
 __global__ __launch_bounds__(RT_BLOCK) void k_root_scan_k(const T *__restrict__ log, uint64_t n, uint32_t head,
                                                           RtKTab tab, uint32_t words, uint32_t m1, uint32_t m2,
@@ -534,182 +506,437 @@ __global__ __launch_bounds__(RT_BLOCK) void k_root_scan_k(const T *__restrict__ 
             __hip_atomic_store(cg, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (__hip_atomic_fetch_add(ct, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == G - 1) {
                 __hip_atomic_store(ct, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(&hout[SMALL_DONE - SMALL_NHITS], gen, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+                __hip_atomic_store(&hout[RT_DONE0], gen, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
             }
         }
     }
 }
 
-// host: the hash set of the roots (see k_root_scan).  S = 1 for up to 32
-// roots (2^b >= 2 k^2 buckets: a multiplier pair without collisions is found
-// in ~1.3 tries on average), else S = 4 with 2^b >= 2k buckets (mean load
-// 1/2).  compact: S = 1 with 2^b >= k^2 / 6 — a table small enough for the
-// kernel arguments (k = 32: 256 words; a collision-free multiplier pair is
-// then found in ~e^(k^2 / 2^(b+1)) = 7 tries, a few hundred host hashes).
-// (S = 4 with 2^b >= 2k, the other small layout, costs the u32 scan 84
-// against 65 µs at configs[4]: four compares per candidate.)  Returns false
-// when no multipliers fit within the attempt limit.
-template <typename T>
-bool rt_scan_table(const T *roots, uint32_t k, RtScanSet &set, std::vector<T> &out, bool compact) {
-    set.S = k <= 32 || compact ? 1 : 4;
-    uint32_t b = 4;
-    const uint64_t want = compact ? ((uint64_t)k * k + 5) / 6 : set.S == 1 ? 2ull * k * k : 2ull * k;
-    while ((1ull << b) < want) ++b;
-    set.shift = 32 - b;
-    const uint32_t nb = 1u << b;
-    set.words = nb * set.S;
-    out.assign(set.words, (T)~(T)0);
-    std::vector<uint32_t> fill(nb);
-    uint64_t st = 0x9E3779B97F4A7C15ull ^ k;
-    for (int attempt = 0; attempt < 1000; ++attempt) {
-        st = splitmix_mix(st + GAMMA);
-        set.m1 = (uint32_t)st | 1u;
-        set.m2 = (uint32_t)(st >> 32) | 1u;
-        std::fill(fill.begin(), fill.end(), 0u);
-        std::fill(out.begin(), out.end(), (T)~(T)0);
-        bool ok = true;
-        for (uint32_t r = 0; r < k && ok; ++r) {
-            const T x = roots[r];
-            uint32_t hh = (uint32_t)x * set.m1;
-            if constexpr (sizeof(T) == 8) hh += (uint32_t)((uint64_t)x >> 32) * set.m2;
-            const uint32_t bi = hh >> set.shift;
-            if (fill[bi] == set.S) ok = false;
-            else out[(size_t)bi * set.S + fill[bi]++] = x;
-        }
-        if (ok) return true;
-    }
-    return false;
+// ---------------------------------------------------------- launchers
+// Workgroups for `units` 16-byte loads, one per lane, at most what the device
+// holds at once.  occ_cache: the kernel's workgroups per CU, asked once per
+// context (the query costs microseconds of a ~100 µs call) at its largest `lds`.
+template <typename KernelT>
+static uint32_t rt_grid(qk_ctx *ctx, KernelT kern, uint64_t units, size_t lds = 0, int *occ_cache = nullptr) {
+    if (ctx->grid_override) return ctx->grid_override;
+    int occ = occ_cache ? *occ_cache : 0;
+    if (!occ && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, RT_BLOCK, lds) != hipSuccess || occ < 1))
+        occ = 1;
+    if (occ_cache) *occ_cache = occ;
+    const uint64_t need = std::max<uint64_t>(1, (units + RT_BLOCK - 1) / RT_BLOCK);
+    return (uint32_t)std::min<uint64_t>(need, (uint64_t)ctx->num_cus * occ);
 }
-template bool rt_scan_table<uint32_t>(const uint32_t *, uint32_t, RtScanSet &, std::vector<uint32_t> &, bool);
-template bool rt_scan_table<uint64_t>(const uint64_t *, uint32_t, RtScanSet &, std::vector<uint64_t> &, bool);
 
-template <typename T>
-int launch_root_scan(qk_ctx *ctx, const T *d_tab, const RtScanSet &set, const T *log, size_t n, int use_stop,
-                     T stop_value, uint64_t *hits, uint64_t cap, uint64_t *counters, uint64_t *hout,
-                     hipStream_t s) {
+// One launch over a log as the kernels read it: `head` entries up to the first
+// 16-byte boundary, then 16-byte loads, `units` of them for the whole log
+// (QK_E_INVAL for a log not aligned to its entry size); launch(head, units)
+// between the profiling events, then the launch's status.
+template <typename T, typename Launch>
+static int rt_launch(qk_ctx *ctx, const T *log, size_t n, hipStream_t s, Launch launch) {
     const uintptr_t a = (uintptr_t)log;
     if (a & (sizeof(T) - 1)) return QK_E_INVAL;
     const uint32_t head = (uint32_t)(((16 - (a & 15)) & 15) / sizeof(T));
-    const size_t lds = (size_t)set.words * sizeof(T);
-    // one nontemporal 16-byte load per lane per iteration: u32 kernel 70 us
-    // against 84 / 78 us with 2 / 4 in flight (profiles/r04/decode_scan_u/);
-    // nontemporal 72 -> 66 us, u64 135 -> 125 us (profiles/r05/decode_nt/)
     const uint64_t units = (n + (16 / sizeof(T)) - 1) / (16 / sizeof(T));
     hipEvent_t e0 = prof_begin(ctx, s);
-#define QK_RS(SS)                                                                                             \
-    hipLaunchKernelGGL((k_root_scan<T, SS>), dim3(rs_grid(ctx, k_root_scan<T, SS>, units, lds)), dim3(RT_BLOCK), \
-                       lds, s, log, (uint64_t)n, head, d_tab, set.words, set.shift, use_stop, stop_value, hits, cap, \
-                       counters, hout, (uint32_t)SMALL_HITPF_N)
-    if (set.S == 1) QK_RS(1);
-    else QK_RS(4);
-#undef QK_RS
+    launch(head, units);
     prof_end(ctx, s, e0);
     QK_HIP_TRY(hipGetLastError());
     return QK_OK;
 }
 
-// ---------------------------------------------------------- launchers
-template <typename KernelT>
-static uint32_t rt_grid(qk_ctx *ctx, KernelT kern, uint64_t units) {
-    if (ctx->grid_override) return ctx->grid_override;
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kern, RT_BLOCK, 0) != hipSuccess || occ < 1) occ = 1;
-    const uint64_t full = (uint64_t)ctx->num_cus * occ;
-    uint64_t need = (units + RT_BLOCK - 1) / RT_BLOCK;
-    if (need < 1) need = 1;
-    return (uint32_t)(need < full ? need : full);
-}
-
-int launch_root_test_u32(qk_ctx *ctx, const uint32_t *d_c, uint32_t d, const uint32_t *log, size_t n,
-                         int use_stop, uint32_t stop_value, uint64_t *hits, uint64_t cap, uint64_t *counters,
-                         hipStream_t s) {
-    const uintptr_t a = (uintptr_t)log;
-    if (a & 3) return QK_E_INVAL;
-    const uint32_t head = (uint32_t)(((16 - (a & 15)) & 15) / 4);
-    const uint64_t units = (n + 3) / 4;
-    hipEvent_t e0 = prof_begin(ctx, s);
+static int launch_root_test(qk_ctx *ctx, const uint32_t *d_c, uint32_t d, const uint32_t *log, size_t n,
+                            int use_stop, uint32_t stop_value, uint64_t *hits, uint64_t cap, uint64_t *counters,
+                            hipStream_t s) {
 #define QK_RT32(DD)                                                                                \
     hipLaunchKernelGGL(k_root_test_u32<DD>, dim3(rt_grid(ctx, k_root_test_u32<DD>, units)),        \
                        dim3(RT_BLOCK), 0, s, log, (uint64_t)n, head, d_c, d, use_stop, stop_value, \
                        hits, cap, counters)
-    switch (d) {
-    case 8: QK_RT32(8); break;
-    case 16: QK_RT32(16); break;
-    case 20: QK_RT32(20); break;
-    case 32: QK_RT32(32); break;
-    default: QK_RT32(0); break;
-    }
+    return rt_launch(ctx, log, n, s, [&](uint32_t head, uint64_t units) {
+        switch (d) {
+        case 8: QK_RT32(8); break;
+        case 16: QK_RT32(16); break;
+        case 20: QK_RT32(20); break;
+        case 32: QK_RT32(32); break;
+        default: QK_RT32(0); break;
+        }
+    });
 #undef QK_RT32
-    prof_end(ctx, s, e0);
-    QK_HIP_TRY(hipGetLastError());
+}
+
+static int launch_root_test(qk_ctx *ctx, const uint64_t *d_c, uint32_t d, const uint64_t *log, size_t n,
+                            int use_stop, uint64_t stop_value, uint64_t *hits, uint64_t cap, uint64_t *counters,
+                            hipStream_t s) {
+    return rt_launch(ctx, log, n, s, [&](uint32_t head, uint64_t units) {
+        if (rt64_use_bsgs(d)) {
+            // d_c holds the limb-shifted table (root_test_begin, rt64_bsgs_table)
+            // one runtime loop over the blocks: an unrolled loop (d / 8 fixed) or
+            // two interleaved candidates made the compiler shuttle every value
+            // around the pinned registers of the p64 step (1300 copies per
+            // evaluation); measured slower
+            hipLaunchKernelGGL(k_root_test_u64_bsgs<0>, dim3(rt_grid(ctx, k_root_test_u64_bsgs<0>, units)),
+                               dim3(RT_BLOCK), 0, s, log, (uint64_t)n, head, d_c, d / 8, (int)(d % 8 != 0), use_stop,
+                               stop_value, hits, cap, counters);
+        } else {
+            hipLaunchKernelGGL(k_root_test_u64, dim3(rt_grid(ctx, k_root_test_u64, units)), dim3(RT_BLOCK), 0, s,
+                               log, (uint64_t)n, head, d_c, d, use_stop, stop_value, hits, cap, counters);
+        }
+    });
+}
+
+// the root-set scan, its set (rootset.h rt_scan_table) copied to d_tab
+template <typename T>
+static int launch_root_scan(qk_ctx *ctx, const T *d_tab, const RtScanSet &set, const T *log, size_t n, int use_stop,
+                            T stop_value, uint64_t *hits, uint64_t cap, uint64_t *counters, uint64_t *hout,
+                            hipStream_t s) {
+    const size_t lds = (size_t)set.words * sizeof(T);
+    // one nontemporal 16-byte load per lane per iteration: u32 kernel 70 us
+    // against 84 / 78 us with 2 / 4 in flight (profiles/r04/decode_scan_u/);
+    // nontemporal 72 -> 66 us, u64 135 -> 125 us (profiles/r05/decode_nt/)
+#define QK_RS(SS)                                                                                             \
+    hipLaunchKernelGGL((k_root_scan<T, SS>), dim3(rt_grid(ctx, k_root_scan<T, SS>, units, lds)), dim3(RT_BLOCK), \
+                       lds, s, log, (uint64_t)n, head, d_tab, set.words, set.shift, use_stop, stop_value, hits, cap, \
+                       counters, hout, (uint32_t)SMALL_HITPF_N)
+    return rt_launch(ctx, log, n, s, [&](uint32_t head, uint64_t units) {
+        if (set.S == 1) QK_RS(1);
+        else QK_RS(4);
+    });
+#undef QK_RS
+}
+
+// ------------------------------------------------------- the host driver
+// Root test by the root-set scan (k_root_scan) or by Horner (k_root_test_*):
+// the same hit list (P(x) == 0 <=> x mod p is a root of P).  The scan costs
+// the host root finding (roots.cpp, ~c d^2) plus an HBM-bound pass; Horner
+// costs d multiply steps per candidate.  Cost model in microseconds from the
+// measurements in DESIGN.md §3.4 (MI355X kernels, EPYC host root finding):
+// the scan is taken when it is cheaper.
+template <typename T> static bool rt_use_scan(const qk_ctx *ctx, uint32_t d, size_t n) {
+    if (d < 2 || d > RT_SCAN_MAXD) return false;          // d = 1: the root is -c_1, Horner is one step
+    if (ctx->knobs.root_test == 1) return false;
+    if (ctx->knobs.root_test == 2) return true;
+    const double nn = (double)n, dd = (double)d;
+    const bool w32 = sizeof(T) == 4;
+    const double horner = nn * dd * (w32 ? 1.43e-7 : 3.8e-7);
+    const double scan = nn * (w32 ? 0.7e-6 : 1.4e-6) + dd * dd * (w32 ? 0.025 : 0.055);
+    return scan < horner;
+}
+
+// The plan of one call: Horner or scan, and for a scan the roots of P, found
+// here and nowhere else; each set is built from them by the form that runs.
+template <typename T>
+static int rt_plan_roots(const qk_ctx *ctx, const T *coeffs, uint32_t d, size_t n, RtPlan<T> &plan) {
+    plan = RtPlan<T>{};
+    if (!n || !rt_use_scan<T>(ctx, d, n)) return QK_OK;
+    plan.roots.resize(d);
+    uint32_t k = 0;
+    if (int rc = Width<T>::roots(coeffs, d, plan.roots.data(), d, &k)) return rc;
+    plan.roots.resize(k);
+    plan.scan = true;
     return QK_OK;
 }
 
-int launch_root_test_u64(qk_ctx *ctx, const uint64_t *d_c, uint32_t d, const uint64_t *log, size_t n,
-                         int use_stop, uint64_t stop_value, uint64_t *hits, uint64_t cap, uint64_t *counters,
-                         hipStream_t s) {
-    const uintptr_t a = (uintptr_t)log;
-    if (a & 7) return QK_E_INVAL;
-    const uint32_t head = (uint32_t)(((16 - (a & 15)) & 15) / 8);
-    const uint64_t units = (n + 1) / 2;
-    hipEvent_t e0 = prof_begin(ctx, s);
-    if (rt64_use_bsgs(ctx, d)) {
-        // d_c holds the limb-shifted table (root_test_begin, rt64_bsgs_table)
-        // one runtime loop over the blocks: an unrolled loop (d / 8 fixed) or
-        // two interleaved candidates made the compiler shuttle every value
-        // around the pinned registers of the p64 step (1300 copies per
-        // evaluation); measured slower
-        hipLaunchKernelGGL(k_root_test_u64_bsgs<0>, dim3(rt_grid(ctx, k_root_test_u64_bsgs<0>, units)),
-                           dim3(RT_BLOCK), 0, s, log, (uint64_t)n, head, d_c, d / 8, (int)(d % 8 != 0), use_stop,
-                           stop_value, hits, cap, counters);
+// the compact set; false: none that fits the kernel arguments (the copy form runs)
+template <typename T> static bool rt_plan_karg_set(RtPlan<T> &plan) {
+    return rt_scan_table<T>(plan.roots.data(), (uint32_t)plan.roots.size(), plan.kset, plan.ktab, true) &&
+           plan.kset.words * sizeof(T) <= RT_KTAB_BYTES;
+}
+// the copy form's set, once; no multiplier pair, or a set past d_small's room: the plan falls back to Horner
+template <typename T> static void rt_plan_copy_set(RtPlan<T> &plan) {
+    if (!plan.scan || plan.set.words) return;
+    plan.scan = rt_scan_table<T>(plan.roots.data(), (uint32_t)plan.roots.size(), plan.set, plan.tab, false) &&
+                plan.set.words * sizeof(T) <= RT_SET_BYTES;
+    if (!plan.scan) plan.tab.clear();
+}
+
+template <typename T> int root_test_plan(const qk_ctx *ctx, const T *coeffs, uint32_t d, size_t n, RtPlan<T> &plan) {
+    if (int rc = rt_plan_roots<T>(ctx, coeffs, d, n, plan)) return rc;
+    rt_plan_copy_set<T>(plan);
+    return QK_OK;
+}
+
+// The copy form, in two phases.  root_test_begin enqueues on s: counters +
+// coefficients (or root set) H2D, the kernel, and for Horner the counters and
+// first hits D2H (the scan writes its hits and stops into the pinned slots
+// itself, so no copy trails the kernel).  root_test_finish waits for s,
+// reruns once with a larger hit buffer if the kernel ran out of room, and
+// returns the hit positions sorted ascending (every hit of the log, not cut
+// at the stop) and the first stop position (n if none or !use_stop).
+template <typename T>
+int root_test_begin(qk_ctx *ctx, const RtPlan<T> &plan, const T *coeffs, uint32_t d, const T *d_log, size_t n,
+                    int use_stop, T stop_value, hipStream_t s) {
+    // d_small: [0] hit count, [1] stop index, [2] the hash multipliers, [3]
+    // stops recorded, from [RT_C] the coefficients or the root set (rootset.h)
+    uint64_t *d_counters = ctx->d_small;
+    T *d_c = (T *)(ctx->d_small + RT_C);
+    uint64_t *h_c = ctx->h_small + RT_C;
+    const RtSlots slots{ctx->h_small};
+    const bool scan = n && plan.scan;
+    size_t cbytes = (size_t)d * sizeof(T);
+    if (scan) {
+        cbytes = (size_t)plan.set.words * sizeof(T);
+        memcpy(h_c, plan.tab.data(), cbytes);
+    } else if constexpr (sizeof(T) == 8) {
+        if (rt64_use_bsgs(d)) cbytes = rt64_bsgs_table(coeffs, d, h_c) * 8;   // limb-shifted table
+        else memcpy(h_c, coeffs, cbytes);
     } else {
-        hipLaunchKernelGGL(k_root_test_u64, dim3(rt_grid(ctx, k_root_test_u64, units)), dim3(RT_BLOCK), 0, s, log,
-                           (uint64_t)n, head, d_c, d, use_stop, stop_value, hits, cap, counters);
+        memcpy(h_c, coeffs, cbytes);
     }
-    prof_end(ctx, s, e0);
-    QK_HIP_TRY(hipGetLastError());
+    // one copy carries the zeroed counters, the scan's hash multipliers and
+    // the table (or coefficients): no counter-initialising launch
+    ctx->h_small[0] = 0;
+    ctx->h_small[1] = ~0ull;
+    ctx->h_small[2] = scan ? (uint64_t)plan.set.m1 | (uint64_t)plan.set.m2 << 32 : 0;
+    ctx->h_small[3] = 0;
+    if (scan) slots.clear();
+    ctx->rt.slots_written();   // this call's hits / stops (or Horner's copy) land in the slots
+    QK_HIP_TRY(hipMemcpyAsync(ctx->d_small, ctx->h_small, (RT_C + (cbytes + 7) / 8) * sizeof(uint64_t),
+                              hipMemcpyHostToDevice, s));
+    if (int rc = ensure_hits(ctx, 4096)) return rc;
+    if (n) {
+        if (scan) {
+            // the scan writes its hits and stops into the slots itself
+            // (rt_record); root_test_finish derives count and stop from them
+            // (a D2H copy of the counters and hits instead measured slower,
+            // profiles/r05/decode_nt/)
+            return launch_root_scan<T>(ctx, d_c, plan.set, d_log, n, use_stop, stop_value, ctx->d_hits,
+                                       (uint64_t)ctx->hits_cap, d_counters, RtSlots{ctx->h_small_dev}.result(), s);
+        }
+        if (int rc = launch_root_test(ctx, d_c, d, d_log, n, use_stop, stop_value, ctx->d_hits,
+                                      (uint64_t)ctx->hits_cap, d_counters, s))
+            return rc;
+    }
+    QK_HIP_TRY(hipMemcpyAsync(slots.result(), d_counters, 16, hipMemcpyDeviceToHost, s));
+    // and the first hits with them: a decode finds ~d hits, so one
+    // synchronisation (not a second, pageable, round trip) returns them
+    QK_HIP_TRY(hipMemcpyAsync(slots.hits(), ctx->d_hits, std::min<size_t>(ctx->hits_cap, SMALL_HITPF_N) * 8,
+                              hipMemcpyDeviceToHost, s));
     return QK_OK;
 }
 
 template <typename T>
-int launch_root_scan_k(qk_ctx *ctx, const std::vector<T> &tabv, const RtScanSet &set, const T *log, size_t n,
-                       int use_stop, T stop_value, uint64_t *hits, uint64_t cap, uint64_t *counters, uint64_t *hout,
-                       uint64_t hbase, uint64_t sbase, uint64_t *done, uint64_t gen, hipStream_t s) {
-    const uintptr_t a = (uintptr_t)log;
-    if (a & (sizeof(T) - 1)) return QK_E_INVAL;
-    if (set.words * sizeof(T) > RT_KTAB_BYTES || set.S != 1) return QK_E_INVAL;
-    RtKTab tab;
-    memcpy(tab.w, tabv.data(), (size_t)set.words * sizeof(T));
-    const uint32_t head = (uint32_t)(((16 - (a & 15)) & 15) / sizeof(T));
-    const size_t lds = (size_t)set.words * sizeof(T);
-    const uint64_t units = (n + (16 / sizeof(T)) - 1) / (16 / sizeof(T));
-    hipEvent_t e0 = prof_begin(ctx, s);
-    // workgroups per CU asked once per context (the runtime's occupancy
-    // query costs microseconds of a ~100 µs call), at the largest table
-    int &occ = ctx->rt_occ_k[sizeof(T) == 8];
-    if (!occ && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_root_scan_k<T, 1>, RT_BLOCK, RT_KTAB_BYTES) !=
-                     hipSuccess || occ < 1))
-        occ = 1;
-    const uint64_t need = std::max<uint64_t>(1, (units + RT_BLOCK - 1) / RT_BLOCK);
-    const uint32_t grid =
-        ctx->grid_override ? ctx->grid_override : (uint32_t)std::min<uint64_t>(need, (uint64_t)ctx->num_cus * occ);
-    hipLaunchKernelGGL((k_root_scan_k<T, 1>), dim3(grid), dim3(RT_BLOCK), lds,
-                       s, log, (uint64_t)n, head, tab, set.words, set.m1, set.m2, set.shift, use_stop, stop_value,
-                       hits, cap, counters, hout, (uint32_t)SMALL_HITPF_N, hbase, sbase, done, gen);
-    prof_end(ctx, s, e0);
-    QK_HIP_TRY(hipGetLastError());
+int root_test_finish(qk_ctx *ctx, const RtPlan<T> &plan, const T *coeffs, uint32_t d, const T *d_log, size_t n,
+                     int use_stop, T stop_value, hipStream_t s, std::vector<uint64_t> &hits, uint64_t &stop_index) {
+    // count and stop: the Horner form copied them; the scan has its slots, or
+    // on overflow the device counters are copied now
+    const RtSlots slots{ctx->h_small};
+    RtSlotRead r;
+    auto counts = [&]() -> int {
+        QK_HIP_TRY(hipStreamSynchronize(s));
+        if (n && plan.scan) {
+            r = slots.read();
+            if (!r.overflow) return QK_OK;
+            QK_HIP_TRY(hipMemcpyAsync(slots.result(), ctx->d_small, 16, hipMemcpyDeviceToHost, s));
+            QK_HIP_TRY(hipStreamSynchronize(s));
+        }
+        r = slots.copied();
+        return QK_OK;
+    };
+    if (int rc = counts()) return rc;
+    if (r.hits > ctx->hits_cap) {   // grow and rerun once (the kernel counts every hit)
+        if (int rc = ensure_hits(ctx, (size_t)r.hits)) return rc;
+        if (int rc = root_test_begin<T>(ctx, plan, coeffs, d, d_log, n, use_stop, stop_value, s)) return rc;
+        if (int rc = counts()) return rc;
+        if (r.hits > ctx->hits_cap) return QK_E_HIP;
+    }
+    const uint64_t cnt = r.hits;
+    hits.resize(cnt);
+    if (cnt && cnt <= std::min<size_t>(ctx->hits_cap, SMALL_HITPF_N)) {
+        memcpy(hits.data(), slots.hits(), cnt * 8);
+    } else if (cnt) {
+        QK_HIP_TRY(hipMemcpyAsync(hits.data(), ctx->d_hits, cnt * 8, hipMemcpyDeviceToHost, s));
+        QK_HIP_TRY(hipStreamSynchronize(s));
+    }
+    std::sort(hits.begin(), hits.end());
+    stop_index = use_stop ? std::min<uint64_t>(r.stop, (uint64_t)n) : (uint64_t)n;
     return QK_OK;
 }
-template int launch_root_scan_k<uint32_t>(qk_ctx *, const std::vector<uint32_t> &, const RtScanSet &,
-                                          const uint32_t *, size_t, int, uint32_t, uint64_t *, uint64_t, uint64_t *,
-                                          uint64_t *, uint64_t, uint64_t, uint64_t *, uint64_t, hipStream_t);
-template int launch_root_scan_k<uint64_t>(qk_ctx *, const std::vector<uint64_t> &, const RtScanSet &,
-                                          const uint64_t *, size_t, int, uint64_t, uint64_t *, uint64_t, uint64_t *,
-                                          uint64_t *, uint64_t, uint64_t, uint64_t *, uint64_t, hipStream_t);
 
-template int launch_root_scan<uint32_t>(qk_ctx *, const uint32_t *, const RtScanSet &, const uint32_t *, size_t, int,
-                                        uint32_t, uint64_t *, uint64_t, uint64_t *, uint64_t *, hipStream_t);
-template int launch_root_scan<uint64_t>(qk_ctx *, const uint64_t *, const RtScanSet &, const uint64_t *, size_t, int,
-                                        uint64_t, uint64_t *, uint64_t, uint64_t *, uint64_t *, hipStream_t);
+// The kernel-argument form (single GPU, the plan's compact set: k = 32 roots
+// -> 256 buckets, 1 KB u32 / 2 KB u64): no H2D copy and no counter reset in
+// front of the scan.  The hit / stop tickets run on from the values the
+// previous call left, in their own words of d_small (SMALL_KT), and the slots
+// are refilled only where the call wrote them (ctx.h qk_rt_karg: the invariant
+// and its steps).  A slot overflow returns 1: the caller reruns by the copy form.
+template <typename T>
+static int root_test_scan_k(qk_ctx *ctx, const RtPlan<T> &plan, const T *d_log, size_t n, int use_stop, T stop_value,
+                            hipStream_t s, std::vector<uint64_t> &h, uint64_t &stop) {
+    if (int e = ensure_hits(ctx, 4096)) return e;
+    qk_rt_karg &rt = ctx->rt;
+    const RtSlots slots{ctx->h_small};
+    if (!rt.valid) {
+        QK_HIP_TRY(hipMemsetAsync(ctx->d_small + SMALL_KT, 0, 4 * sizeof(uint64_t), s));
+        rt.tickets_reset();
+    }
+    if (!rt.slots_clean) slots.clear();
+    rt.slots_written();
+    const uint64_t gen = ++rt.gen;
+    const RtScanSet &set = plan.kset;
+    const size_t lds = (size_t)set.words * sizeof(T);   // <= RT_KTAB_BYTES, S = 1 (rt_plan_karg_set)
+    RtKTab tab;
+    memcpy(tab.w, plan.ktab.data(), lds);
+    if (int e = rt_launch(ctx, d_log, n, s, [&](uint32_t head, uint64_t units) {
+            const uint32_t grid = rt_grid(ctx, k_root_scan_k<T, 1>, units, RT_KTAB_BYTES, &rt.occ[sizeof(T) == 8]);
+            hipLaunchKernelGGL((k_root_scan_k<T, 1>), dim3(grid), dim3(RT_BLOCK), lds, s, d_log, (uint64_t)n, head, tab,
+                               set.words, set.m1, set.m2, set.shift, use_stop, stop_value, ctx->d_hits,
+                               (uint64_t)ctx->hits_cap, ctx->d_small + SMALL_KT, RtSlots{ctx->h_small_dev}.result(),
+                               (uint32_t)SMALL_HITPF_N, rt.hbase, rt.sbase, ctx->d_small + RT_DONE, gen);
+        })) {
+        rt.tickets_lost();
+        return e;
+    }
+    // wait by polling the completion mark the kernel's last workgroup writes
+    // (k_root_scan_k: the result is in the slots ~3-5 µs before the stream
+    // reports the kernel done), the stream asked now and then: an error fails
+    // the call; a finished stream without the mark (completion tickets left
+    // off by an earlier aborted launch) still has the result, and the
+    // tickets are cleared for the next launch
+    const volatile uint64_t *done = slots.done();
+    for (unsigned spin = 0;; ++spin) {
+        if (*done == gen) break;
+        if ((spin & 63) == 63) {
+            const hipError_t q = hipStreamQuery(s);
+            if (q != hipSuccess && q != hipErrorNotReady) {
+                rt.tickets_lost();
+                return QK_E_HIP;
+            }
+            if (q == hipSuccess) {
+                if (*done == gen) break;
+                QK_HIP_TRY(hipMemsetAsync(ctx->d_small + RT_DONE, 0, RT_DONE_WORDS * sizeof(uint64_t), s));
+                break;
+            }
+        }
+        if (spin >= 200000) std::this_thread::sleep_for(std::chrono::microseconds(5));
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    const RtSlotRead r = slots.read();
+    if (r.overflow) {   // past the slots: the copy form reruns it
+        rt.tickets_lost();
+        return 1;
+    }
+    h.assign(slots.hits(), slots.hits() + r.hits);
+    slots.restore(r);
+    rt.call_done(r);
+    std::sort(h.begin(), h.end());
+    stop = use_stop ? std::min<uint64_t>(r.stop, (uint64_t)n) : (uint64_t)n;
+    return QK_OK;
+}
+
+// plan -> the kernel-argument scan if it may run -> else, or on its slot overflow, the copy form, same plan
+template <typename T>
+static int root_test_impl(qk_ctx *ctx, const T *coeffs, uint32_t d, const T *d_log, size_t n, int use_stop,
+                          T stop_value, uint64_t *hits, size_t cap, size_t *n_hits, void *stream,
+                          uint64_t *stop_index = nullptr) {
+    if (!ctx || !n_hits || (d && !coeffs) || (n && !d_log)) return QK_E_INVAL;
+    *n_hits = 0;
+    if (stop_index) *stop_index = n;
+    if (n == 0) return QK_OK;
+    if (d == 0) {
+        if (!stop_index || !use_stop) return QK_OK; // P == 1 has no roots
+        // no roots, but a shard caller still needs the stop position: the
+        // degree-0 launch tests nothing and only records the stop
+    }
+    if (d > QK_MAX_THRESHOLD) return QK_E_THRESHOLD;
+    if (!is_device_ptr(d_log)) return QK_E_INVAL;
+    std::lock_guard<std::mutex> g(ctx->mu);
+    QK_HIP_TRY(hipSetDevice(ctx->device));
+    hipStream_t s = pick_stream(ctx, stream);
+    std::vector<uint64_t> h;
+    uint64_t stop = n;
+    RtPlan<T> plan;
+    if (int rc = rt_plan_roots<T>(ctx, coeffs, d, n, plan)) return rc;
+    int ov = 1;
+    if (ctx->knobs.rt_karg && plan.scan && rt_plan_karg_set<T>(plan)) {
+        ov = root_test_scan_k<T>(ctx, plan, d_log, n, use_stop, stop_value, s, h, stop);
+        if (ov < 0) return ov;
+    }
+    if (ov) {   // Horner, a set too large for the kernel arguments, or a slot overflow
+        rt_plan_copy_set<T>(plan);
+        if (int rc = root_test_begin<T>(ctx, plan, coeffs, d, d_log, n, use_stop, stop_value, s)) return rc;
+        if (int rc = root_test_finish<T>(ctx, plan, coeffs, d, d_log, n, use_stop, stop_value, s, h, stop)) return rc;
+    }
+    const size_t m = (size_t)(std::lower_bound(h.begin(), h.end(), stop) - h.begin());
+    if (stop_index) *stop_index = stop;
+    *n_hits = m;
+    if (m > cap || (m && !hits)) return QK_E_CAPACITY;
+    std::copy(h.begin(), h.begin() + m, hits);
+    return QK_OK;
+}
+
+// The kernel-argument form first: the code object keeps its kernels in the
+// order it always had (make asm is compared); then comm.hip's two-phase form.
+template int root_test_scan_k<uint32_t>(qk_ctx *, const RtPlan<uint32_t> &, const uint32_t *, size_t, int, uint32_t,
+                                        hipStream_t, std::vector<uint64_t> &, uint64_t &);
+template int root_test_scan_k<uint64_t>(qk_ctx *, const RtPlan<uint64_t> &, const uint64_t *, size_t, int, uint64_t,
+                                        hipStream_t, std::vector<uint64_t> &, uint64_t &);
+template int root_test_plan<uint32_t>(const qk_ctx *, const uint32_t *, uint32_t, size_t, RtPlan<uint32_t> &);
+template int root_test_plan<uint64_t>(const qk_ctx *, const uint64_t *, uint32_t, size_t, RtPlan<uint64_t> &);
+template int root_test_begin<uint32_t>(qk_ctx *, const RtPlan<uint32_t> &, const uint32_t *, uint32_t,
+                                       const uint32_t *, size_t, int, uint32_t, hipStream_t);
+template int root_test_begin<uint64_t>(qk_ctx *, const RtPlan<uint64_t> &, const uint64_t *, uint32_t,
+                                       const uint64_t *, size_t, int, uint64_t, hipStream_t);
+template int root_test_finish<uint32_t>(qk_ctx *, const RtPlan<uint32_t> &, const uint32_t *, uint32_t,
+                                        const uint32_t *, size_t, int, uint32_t, hipStream_t, std::vector<uint64_t> &,
+                                        uint64_t &);
+template int root_test_finish<uint64_t>(qk_ctx *, const RtPlan<uint64_t> &, const uint64_t *, uint32_t,
+                                        const uint64_t *, size_t, int, uint64_t, hipStream_t, std::vector<uint64_t> &,
+                                        uint64_t &);
+
+// decode_with_log: to_coeffs(diff) on the host, then the root test
+template <typename T>
+static int decode_impl(qk_ctx *ctx, const typename Width<T>::quack *diff, const T *d_log, size_t n, int stop_at_last,
+                       uint64_t *hits, size_t cap, size_t *n_hits, void *stream) {
+    if (!ctx || !diff || !n_hits) return QK_E_INVAL;
+    *n_hits = 0;
+    if (diff->count == 0) return QK_OK;
+    std::vector<T> c(diff->threshold ? diff->threshold : 1);
+    uint32_t d = 0;
+    if (int rc = Width<T>::to_coeffs(diff, c.data(), (uint32_t)c.size(), &d)) return rc;
+    return root_test_impl<T>(ctx, c.data(), d, d_log, n, stop_at_last && diff->has_last, diff->last_value, hits, cap,
+                             n_hits, stream);
+}
 
 } // namespace qk
+
+using namespace qk;
+
+extern "C" {
+
+int qk_u32_root_test_device(qk_ctx *ctx, const uint32_t *coeffs, uint32_t d, const uint32_t *d_log, size_t n,
+                            int stop_at_value, uint32_t stop_value, uint64_t *hits, size_t cap, size_t *n_hits,
+                            void *stream) {
+    return root_test_impl<uint32_t>(ctx, coeffs, d, d_log, n, stop_at_value, stop_value, hits, cap, n_hits, stream);
+}
+
+int qk_u64_root_test_device(qk_ctx *ctx, const uint64_t *coeffs, uint32_t d, const uint64_t *d_log, size_t n,
+                            int stop_at_value, uint64_t stop_value, uint64_t *hits, size_t cap, size_t *n_hits,
+                            void *stream) {
+    return root_test_impl<uint64_t>(ctx, coeffs, d, d_log, n, stop_at_value, stop_value, hits, cap, n_hits, stream);
+}
+
+int qk_u32_root_test_shard_device(qk_ctx *ctx, const uint32_t *coeffs, uint32_t d, const uint32_t *d_log, size_t n,
+                                  int stop_at_value, uint32_t stop_value, uint64_t *hits, size_t cap,
+                                  size_t *n_hits, uint64_t *stop_index, void *stream) {
+    if (!stop_index) return QK_E_INVAL;
+    return root_test_impl<uint32_t>(ctx, coeffs, d, d_log, n, stop_at_value, stop_value, hits, cap, n_hits, stream,
+                                    stop_index);
+}
+
+int qk_u64_root_test_shard_device(qk_ctx *ctx, const uint64_t *coeffs, uint32_t d, const uint64_t *d_log, size_t n,
+                                  int stop_at_value, uint64_t stop_value, uint64_t *hits, size_t cap,
+                                  size_t *n_hits, uint64_t *stop_index, void *stream) {
+    if (!stop_index) return QK_E_INVAL;
+    return root_test_impl<uint64_t>(ctx, coeffs, d, d_log, n, stop_at_value, stop_value, hits, cap, n_hits, stream,
+                                    stop_index);
+}
+
+int qk_u32_decode_device(qk_ctx *ctx, const qk_u32 *diff, const uint32_t *d_log, size_t n, int stop_at_last,
+                         uint64_t *hits, size_t cap, size_t *n_hits, void *stream) {
+    return decode_impl<uint32_t>(ctx, diff, d_log, n, stop_at_last, hits, cap, n_hits, stream);
+}
+
+int qk_u64_decode_device(qk_ctx *ctx, const qk_u64 *diff, const uint64_t *d_log, size_t n, int stop_at_last,
+                         uint64_t *hits, size_t cap, size_t *n_hits, void *stream) {
+    return decode_impl<uint64_t>(ctx, diff, d_log, n, stop_at_last, hits, cap, n_hits, stream);
+}
+
+} // extern "C"

@@ -268,6 +268,73 @@ def test_host_channel_decode_stop_in_middle_shard():
     assert all(got == want for _, got in res)
 
 
+@pytest.mark.parametrize("stop", [False, True])
+@pytest.mark.parametrize("n_dup", [0, 5000])
+@pytest.mark.parametrize("bits", [32, 64])
+def test_host_channel_decode_by_root_set_scan(bits, n_dup, stop):
+    """The sharded decode with the root-set scan forced on every rank (knob
+    root_test = 2; small logs otherwise pick Horner): one plan, its roots found
+    once, shared by the shards; the scan's set by the H2D copy form, its hits
+    through the pinned slots.  With 5000 copies of one dropped id in rank 1's
+    shard that rank runs past its slots and past the 4096-entry hit buffer
+    (the counters read back, the buffer grown, the scan rerun from the same
+    plan).  Every rank returns the single-GPU Horner answer, which is the
+    numpy positions of the dropped ids cut at the stop."""
+    import torch
+    import sidekick_amd as sk
+    world, n_total, d = 3, 30_000, 30
+    dup_at = 12_000                                   # rank 1 holds [10 000, 20 000)
+    Q = sk.PowerSumQuackU32 if bits == 32 else sk.PowerSumQuackU64
+    p = (1 << 32) - 5 if bits == 32 else (1 << 64) - 59
+    a = (coracle.splitmix_u32 if bits == 32 else coracle.splitmix_u64)(0x5CA0 + bits, n_total).copy()
+    rng = np.random.default_rng(bits + n_dup)
+    free = np.setdiff1d(np.arange(n_total - 1), np.arange(dup_at, dup_at + 5000))   # not the copies, not the last id
+    drops = np.sort(rng.choice(free, d, replace=False))
+    assert len({int(v) % p for v in a[drops]}) == d
+    if n_dup:
+        a[dup_at:dup_at + n_dup] = a[drops[0]]
+    keep = np.ones(n_total, bool)
+    keep[drops] = False
+    dt = np.int32 if bits == 32 else np.int64
+    log = torch.from_numpy(a.view(dt)).cuda()
+    diff, recv = Q(32), Q(32)
+    diff.insert_batch(log)
+    recv.insert_batch(torch.from_numpy(a[keep].view(dt)).cuda())
+    diff.sub_assign(recv)
+    assert diff.count() == d
+    coeffs = diff.to_coeffs()
+    assert len(coeffs) == d
+
+    last = diff.last_value()
+    assert last == int(a[-1])
+    dropped = {int(v) % p for v in a[drops]}
+    pos = [i for i, v in enumerate(a.tolist()) if v % p in dropped]
+    cut = int(np.flatnonzero(a == a[-1])[0]) if stop else n_total
+    want = [i for i in pos if i < cut]
+    assert len(want) == d + n_dup and set(drops.tolist()) <= set(want)
+
+    ctx = sk.get_context(0)
+    ctx.set_knob("root_test", 1)
+    try:
+        assert diff.root_test(coeffs, log, stop_value=last if stop else None) == want
+    finally:
+        ctx.set_knob("root_test", 0)
+    bounds = _shards(n_total, world)
+
+    def rank_fn(r, comm):
+        comm.context(0).set_knob("root_test", 2)
+        try:
+            s, c = bounds[r]
+            return comm.decode_sharded(diff if r == 0 else None, [log[s:s + c]], bits=bits, stop_at_last=stop)
+        finally:
+            comm.context(0).set_knob("root_test", 0)
+
+    res = _run_ranks(world, rank_fn)
+    assert all(ok for ok, _ in res), res
+    for _, got in res:
+        assert got == want
+
+
 def test_host_channel_failure_on_one_rank_errors_everywhere_no_hang():
     """A bad shard on one rank (misaligned device pointer): the sharded encode
     returns its error on that rank and QK_E_PEER on the root, q untouched; the

@@ -360,6 +360,83 @@ def test_scan_kernel_args_tickets_run_on(root_test_mode):
     assert results[1] == results[0]
 
 
+def _log_with_hits(rng, bits, n, roots, nhit, lead=0):
+    """A random log of n entries (after `lead` entries in front of the device
+    view) in which exactly nhit positions hold one of `roots`, every root at
+    least once: (host log, device view, sorted hit positions)."""
+    dt = np.uint32 if bits == 32 else np.uint64
+    p = np.uint64(qo.MOD[bits])
+    ra = np.array(roots, dtype=dt)
+    full = rng.integers(0, 1 << bits, size=lead + n, dtype=np.uint64).astype(dt)
+    log = full[lead:]
+    log[np.isin(log.astype(np.uint64) % p, ra.astype(np.uint64) % p)] = 7
+    pos = np.sort(rng.choice(n, size=nhit, replace=False))
+    log[pos] = ra[rng.permutation(nhit) % len(ra)]
+    assert np.flatnonzero(np.isin(log.astype(np.uint64) % p, ra.astype(np.uint64) % p)).tolist() == pos.tolist()
+    return log, dev(full, bits)[lead:], pos
+
+
+@pytest.mark.parametrize("bits,fit", [(32, 55), (64, 39)])
+def test_scan_fit_boundary_tickets_across_forms(bits, fit):
+    """The largest root set that fits the kernel arguments (55 roots u32, 39
+    u64), one root more (the set by the H2D copy), then the largest again on
+    the same context: the kernel-argument form's tickets run on across the
+    copy form's call.  Fresh distinct roots per call, planted in a log of 4099
+    entries whose device view starts one entry past a 16-byte boundary, one
+    root twice, and a stop value that cuts the last hits; each call against
+    the oracle."""
+    rng = np.random.default_rng(1000 + bits)
+    n = 4099
+    oracle = coracle.root_test_u32 if bits == 32 else coracle.root_test_u64
+    for call, d in enumerate((fit, fit + 1, fit)):
+        roots = [int(r) + 100 + (call << 24) for r in rng.choice(1 << 20, size=d, replace=False)]
+        log, d_log, pos = _log_with_hits(rng, bits, n, roots, d + 1, lead=1)
+        assert d_log.data_ptr() % 16 == bits // 8
+        q = QT(bits)(d)
+        for r in roots:
+            q.insert(r)
+        c = q.to_coeffs()
+        assert len(c) == d
+        want, _ = oracle(c, log)
+        assert want.tolist() == pos.tolist()
+        assert q.root_test(c, d_log) == want.tolist(), (call, d)
+        stop_value = 0xFEEDBEE
+        assert stop_value not in log.tolist()
+        spos = int(next(i for i in range(int(pos[-3]) + 1, n) if i not in set(pos.tolist())))
+        log2 = log.copy()
+        log2[[spos, n - 1 if n - 1 not in pos else n - 2]] = stop_value
+        full2 = np.concatenate([log2[:1], log2])
+        want2 = [h for h in oracle(c, log2)[0].tolist() if h < spos]
+        assert len(want2) < len(want) and len(want2) >= d - 2
+        assert q.root_test(c, dev(full2, bits)[1:], stop_value=stop_value) == want2, (call, d)
+
+
+@pytest.mark.parametrize("bits", [32, 64])
+def test_scan_overflow_rerun_changes_set_layout(bits):
+    """36 distinct roots: the compact set fits the kernel arguments, the set
+    of the copy form is the four-slot layout.  1100 hits overflow the pinned
+    slots, so the call is rerun by the copy form from the same plan (the roots
+    found once, the other set built from them); a 3-hit call follows at once
+    on the same context (its tickets reset, its slots refilled).  Both against
+    numpy set membership."""
+    rng = np.random.default_rng(36 + bits)
+    roots = [int(r) + 100 for r in rng.choice(1 << 24, size=36, replace=False)]
+    log, d_log, pos = _log_with_hits(rng, bits, 20_000, roots, 1100)
+    q = QT(bits)(36)
+    for r in roots:
+        q.insert(r)
+    few = [int(r) + (1 << 30) for r in rng.choice(1 << 24, size=3, replace=False)]
+    log3, d_log3, pos3 = _log_with_hits(rng, bits, 20_000, few, 3)
+    q3 = QT(bits)(3)
+    for r in few:
+        q3.insert(r)
+    c, c3 = q.to_coeffs(), q3.to_coeffs()
+    assert len(c) == 36 and len(c3) == 3
+    assert q.root_test(c, d_log) == pos.tolist()
+    assert q3.root_test(c3, d_log3) == pos3.tolist()
+    assert q.root_test(c, d_log) == pos.tolist()
+
+
 @pytest.mark.parametrize("off,n", [(1, 100_007), (2, 100_000), (3, 5), (0, 17)])
 def test_scan_ragged_and_misaligned(off, n, root_test_mode):
     """The root test over a log starting 0-3 entries past a 16-byte boundary
