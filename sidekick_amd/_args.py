@@ -73,6 +73,10 @@ def _device_array(a, bits: int):
 def _host_array(a, bits: int) -> np.ndarray:
     dt = np.uint32 if bits == 32 else np.uint64
     arr = np.asarray(a)
+    if arr.dtype.kind == "f" and not isinstance(a, np.ndarray):
+        # a sequence of Python ints on both sides of 2^63 comes out of numpy as
+        # float64 (53 bits); converted with the dtype given, every id is exact
+        arr = np.asarray(a, dtype=dt)
     if arr.dtype != dt:
         arr = arr.astype(dt)
     return np.ascontiguousarray(arr)

@@ -178,3 +178,20 @@ def test_parse_packs_the_sketches_in_order():
     assert (r.nseg, r.t, r.dev) == (3, 4, None) and r.ptr.value
     assert r.keep.raw[:3 * 32] == b"".join(q._buf.raw for q in qs)
     r.need_threshold("mine")
+
+
+# ---------------------------------------------------------------- host arrays
+def test_host_array_keeps_python_ints_on_both_sides_of_2_63_exact():
+    """numpy makes float64 of such a sequence (53 bits); the ids must arrive bit for bit."""
+    from sidekick_amd._args import _host_array
+    ids = [1, 2**63 + 5, 2**64 - 60, 3, 2**53 + 1]
+    arr = _host_array(ids, 64)
+    assert arr.dtype == np.uint64 and [int(v) for v in arr] == ids
+    assert [int(v) for v in _host_array([7, 2**32 - 1], 32)] == [7, 2**32 - 1]
+    # arrays and same-sided sequences as before
+    assert _host_array(np.array([-1], dtype=np.int64), 64)[0] == 2**64 - 1
+    assert _host_array(np.array([1.0, 2.0]), 64).tolist() == [1, 2]
+    q = sk.PowerSumQuackU64(2)
+    q.insert(2**63 + 5)
+    q.insert(3)
+    assert q.decode_host(ids) == [1, 3]
