@@ -6,10 +6,10 @@
 // (a < NA; A_0 = 1), so S_{m+1} = sum_i A_a(x_i) * B_b(x_i): NB-1 + NA-2
 // lazy modmuls per id, then (NA-1)*NB 32x32->64 multiply-accumulates into
 // 64-bit accumulators whose wraps are counted (2^64 == 25 mod p), plus NB
-// 32-bit adds for the a = 0 row whose wraps are counted (2^32 == 5 mod p).
+// 64-bit adds for the a = 0 row, which cannot wrap.
 //
-// Wrap counting, per accumulator group of four (template knobs):
-//   VALU form   v_mad_u64_u32 / v_add_co_u32 writes its carry to an SGPR pair,
+// Wrap counting, per accumulator group of four (Cfg SG):
+//   VALU form   v_mad_u64_u32 writes its carry to an SGPR pair,
 //               v_addc_co_u32 adds it into a per-lane 32-bit counter.  gfx950
 //               needs two wait states between a VALU SGPR write and a VALU
 //               carry-in read (hipcc pads with s_nop), so four ops with four
@@ -53,7 +53,7 @@ __device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int m) {
     return ((uint64_t)hi << 32) | lo;
 }
 
-// ---- multiply-accumulate and add groups, carries counted ------------------
+// ---- multiply-accumulate groups, carries counted ---------------------------
 // The carry masks live in explicitly named SGPR pairs, and consecutive groups
 // alternate between two disjoint sets (SET 0: s[40:47] + temp s56, SET 1:
 // s[48:55] + temp s57).  hipcc treats an inline-asm block's SGPR definitions
@@ -77,24 +77,6 @@ __device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int m) {
     "v_mad_u64_u32 %1, " P1 ", %8, %10, %1\n\t"                                                        \
     "v_mad_u64_u32 %2, " P2 ", %8, %11, %2\n\t"                                                        \
     "v_mad_u64_u32 %3, " P3 ", %8, %12, %3\n\t"                                                        \
-    "s_bcnt1_i32_b64 " T ", " P0 "\n\ts_add_u32 %4, %4, " T "\n\t"                                          \
-    "s_bcnt1_i32_b64 " T ", " P1 "\n\ts_add_u32 %5, %5, " T "\n\t"                                          \
-    "s_bcnt1_i32_b64 " T ", " P2 "\n\ts_add_u32 %6, %6, " T "\n\t"                                          \
-    "s_bcnt1_i32_b64 " T ", " P3 "\n\ts_add_u32 %7, %7, " T
-#define QK_ADD4V(P0, P1, P2, P3)                                                                       \
-    "v_add_co_u32_e64 %0, " P0 ", %0, %8\n\t"                                                          \
-    "v_add_co_u32_e64 %1, " P1 ", %1, %9\n\t"                                                          \
-    "v_add_co_u32_e64 %2, " P2 ", %2, %10\n\t"                                                         \
-    "v_add_co_u32_e64 %3, " P3 ", %3, %11\n\t"                                                         \
-    "v_addc_co_u32_e64 %4, " P0 ", %4, 0, " P0 "\n\t"                                                  \
-    "v_addc_co_u32_e64 %5, " P1 ", %5, 0, " P1 "\n\t"                                                  \
-    "v_addc_co_u32_e64 %6, " P2 ", %6, 0, " P2 "\n\t"                                                  \
-    "v_addc_co_u32_e64 %7, " P3 ", %7, 0, " P3
-#define QK_ADD4S(P0, P1, P2, P3, T)                                                                       \
-    "v_add_co_u32_e64 %0, " P0 ", %0, %8\n\t"                                                          \
-    "v_add_co_u32_e64 %1, " P1 ", %1, %9\n\t"                                                          \
-    "v_add_co_u32_e64 %2, " P2 ", %2, %10\n\t"                                                         \
-    "v_add_co_u32_e64 %3, " P3 ", %3, %11\n\t"                                                         \
     "s_bcnt1_i32_b64 " T ", " P0 "\n\ts_add_u32 %4, %4, " T "\n\t"                                          \
     "s_bcnt1_i32_b64 " T ", " P1 "\n\ts_add_u32 %5, %5, " T "\n\t"                                          \
     "s_bcnt1_i32_b64 " T ", " P2 "\n\ts_add_u32 %6, %6, " T "\n\t"                                          \
@@ -167,37 +149,6 @@ __device__ __forceinline__ void mac4ps(uint64_t &a0, uint64_t &a1, uint64_t &a2,
             : "v"(l0), "v"(r0), "v"(l1), "v"(r1), "v"(l2), "v"(r2), "v"(l3), "v"(r3)
             : "scc", "s57", QK_CLOB1);
 }
-// lo_j += b_j (32-bit), wraps counted per lane (c_j) or per wave (s_j)
-template <int SET>
-__device__ __forceinline__ void add4v(uint32_t &l0, uint32_t &l1, uint32_t &l2, uint32_t &l3, uint32_t &c0,
-                                      uint32_t &c1, uint32_t &c2, uint32_t &c3, uint32_t b0, uint32_t b1,
-                                      uint32_t b2, uint32_t b3) {
-    if constexpr (SET == 0)
-        asm volatile(QK_EXPAND(QK_ADD4V, QK_SET0)
-            : "+v"(l0), "+v"(l1), "+v"(l2), "+v"(l3), "+v"(c0), "+v"(c1), "+v"(c2), "+v"(c3)
-            : "v"(b0), "v"(b1), "v"(b2), "v"(b3)
-            : QK_CLOB0);
-    else
-        asm volatile(QK_EXPAND(QK_ADD4V, QK_SET1)
-            : "+v"(l0), "+v"(l1), "+v"(l2), "+v"(l3), "+v"(c0), "+v"(c1), "+v"(c2), "+v"(c3)
-            : "v"(b0), "v"(b1), "v"(b2), "v"(b3)
-            : QK_CLOB1);
-}
-template <int SET>
-__device__ __forceinline__ void add4s(uint32_t &l0, uint32_t &l1, uint32_t &l2, uint32_t &l3, uint32_t &s0,
-                                      uint32_t &s1, uint32_t &s2, uint32_t &s3, uint32_t b0, uint32_t b1,
-                                      uint32_t b2, uint32_t b3) {
-    if constexpr (SET == 0)
-        asm volatile(QK_EXPAND(QK_ADD4S, QK_SET0T)
-            : "+v"(l0), "+v"(l1), "+v"(l2), "+v"(l3), "+s"(s0), "+s"(s1), "+s"(s2), "+s"(s3)
-            : "v"(b0), "v"(b1), "v"(b2), "v"(b3)
-            : "scc", "s56", QK_CLOB0);
-    else
-        asm volatile(QK_EXPAND(QK_ADD4S, QK_SET1T)
-            : "+v"(l0), "+v"(l1), "+v"(l2), "+v"(l3), "+s"(s0), "+s"(s1), "+s"(s2), "+s"(s3)
-            : "v"(b0), "v"(b1), "v"(b2), "v"(b3)
-            : "scc", "s57", QK_CLOB1);
-}
 // leftovers for NB % 4 != 0 (t = 17..24 uses NB = 6): compiler-allocated
 // carries with explicit wait states
 __device__ __forceinline__ void mac2v(uint64_t &a0, uint64_t &a1, uint32_t &c0, uint32_t &c1, uint32_t A,
@@ -211,22 +162,10 @@ __device__ __forceinline__ void mac2v(uint64_t &a0, uint64_t &a1, uint32_t &c0, 
         : "+v"(a0), "+v"(a1), "+v"(c0), "+v"(c1), "=&s"(k0), "=&s"(k1)
         : "v"(A), "v"(b0), "v"(b1));
 }
-__device__ __forceinline__ void add2v(uint32_t &l0, uint32_t &l1, uint32_t &c0, uint32_t &c1, uint32_t b0,
-                                      uint32_t b1) {
-    uint64_t k0, k1;
-    asm("v_add_co_u32_e64 %0, %4, %0, %6\n\t"
-        "v_add_co_u32_e64 %1, %5, %1, %7\n\t"
-        "s_nop 0\n\t"
-        "v_addc_co_u32_e64 %2, %4, %2, 0, %4\n\t"
-        "v_addc_co_u32_e64 %3, %5, %3, 0, %5"
-        : "+v"(l0), "+v"(l1), "+v"(c0), "+v"(c1), "=&s"(k0), "=&s"(k1)
-        : "v"(b0), "v"(b1));
-}
 
 // ---- a = 0 row as 64-bit multiply-adds: acc_j += b_j * 1 ------------------
 // acc < 2^64 for < 2^32 adds of 32-bit values, so no carry is counted: one
-// VALU per add (its carry-out is dead) instead of an add + add-with-carry pair
-// (both SGPR-writing VALU ops, ~4 SIMD cycles each on gfx950: tools/ubench_issue.hip).
+// VALU per add (its carry-out is dead).
 #define QK_ROW4M(P0, P1, P2, P3)                                                                       \
     "v_mad_u64_u32 %0, " P0 ", %4, 1, %0\n\t"                                                          \
     "v_mad_u64_u32 %1, " P1 ", %5, 1, %1\n\t"                                                          \
@@ -257,68 +196,49 @@ __device__ __forceinline__ void row2m(uint64_t &a0, uint64_t &a1, uint32_t b0, u
 // ---- configuration ----------------------------------------------------------
 //  NB, NA  baby / giant steps (NB even)
 //  SG      the first SG 4-wide accumulator groups count their wraps on the
-//          scalar unit.  Group numbering: the a = 0 row's groups are
-//          g = 0 .. NB/4-1 (only when ROW0 == 0), MAC row a (1..NA-1) has
-//          g = a*(NB/4) + b/4.  NB % 4 leftovers always use the VALU form.
-//  ROW0    0: a = 0 row as 32-bit adds with counted wraps; 1: 64-bit mads
-//  FOLD    0: lazy fold with an SGPR-writing add (wrap = its carry, ORed on the
-//          scalar unit); 1: plain add, wraps caught by a per-lane minimum of
-//          the fold results (a wrapped fold leaves a value < 25, field.h)
-//  PAIR    interleave the power chains of two ids
-//  OFF     offset pass (thresholds > 80, several passes over the ids): the
-//          giants are x^(base + a*NB) for a = 0..NA-1 with a runtime base
-//          (a multiple of NB), so every row is a MAC row (no a = 0 sum row)
-//          and the pass yields powers base+1 .. base+NB*NA
+//          scalar unit.  Group numbering: MAC row a (1..NA-1; an offset pass:
+//          0..NA-1) has g = a*(NB/4) + b/4; the a = 0 sum row counts nothing.
+//          NB % 4 leftovers always use the VALU form.
+//  PRIO    wave priority (s_setprio) over each id's accumulation: row 0 at 1
+//          and the MAC rows with their scalar wrap counts at 2, the powers at
+//          0.  false: no priority change.
 //  XC      bit 0 (offset passes) — x^base per id read from the previous
 //          pass's cache instead of square-and-multiply; bit 1 — the next
 //          pass's x^base written per id (one more product): x^(base + NB*NA)
 //          after an offset pass, x^(NB*NA) after a plain one (pass 0)
-//  TREE    babies by a product tree (x^(h+l) = x^h x^l, h the highest power
-//          of two below): the same NB - 1 lazy modmuls at dependency depth
-//          log2(NB) instead of NB - 1 (plain passes with min-tracked folds)
+//  OFF     offset pass (thresholds > 80, several passes over the ids): the
+//          giants are x^(base + a*NB) for a = 0..NA-1 with a runtime base
+//          (a multiple of NB), so every row is a MAC row (no a = 0 sum row)
+//          and the pass yields powers base+1 .. base+NB*NA
 //  BASIS   (CfgBasis) 32 powers from the nine-power basis of basis32.h instead
 //          of the (8, 4) grid: 8 lazy products, 8 direct adds and 24 pair MACs
 //          per id in the same accumulators (slot -> power from the table,
 //          finish())
-template <int NB_, int NA_, int SG_, int ROW0_ = 1, int FOLD_ = 1, bool PAIR_ = false, bool OFF_ = false,
-          int XC_ = 0, bool TREE_ = false, int PRIO_ = 0>
+template <int NB_, int NA_, int SG_, bool PRIO_ = false, int XC_ = 0, bool OFF_ = false>
 struct Cfg {
     static constexpr bool BASIS = false;   // CfgBasis (below) sets it
     static constexpr bool FILT = false;    // ... and this
-    // PRIO  wave priority (s_setprio) over the accumulation: 4 (the product)
-    //       row 0 at 1 and the MAC rows with their scalar wrap counts at 2,
-    //       the powers at 0; (measurements) 1 the whole accumulation at 1,
-    //       2 the powers raised instead, 3 the MAC rows only, 5 / 6 other levels
-    static constexpr int PRIO = PRIO_;
-    static constexpr int NB = NB_, NA = NA_, SG = SG_, ROW0 = ROW0_, FOLD = FOLD_, XC = XC_;
-    static constexpr bool TREE = TREE_;
-    static_assert(!TREE_ || (!OFF_ && FOLD_ == 1), "product-tree babies: plain passes, min-tracked folds");
-    static constexpr bool PAIR = PAIR_, OFF = OFF_;
+    static constexpr int NB = NB_, NA = NA_, SG = SG_, XC = XC_;
+    static constexpr bool PRIO = PRIO_, OFF = OFF_;
     static_assert(OFF_ || (XC_ & 1) == 0, "only an offset pass reads x^base");
-    static_assert(!XC_ || FOLD_ == 1, "the x^base cache goes with min-tracked folds");
     static constexpr int ROWS = OFF_ ? NA_ : NA_ - 1;   // MAC rows
     static constexpr int ROW1 = OFF_ ? 0 : 1;           // group-row number of the first MAC row
     static_assert(NB % 2 == 0 && (NA >= 2 || (OFF_ && NA == 1)), "NB even, NA >= 2 (1: offset pass)");
-    static_assert(!OFF_ || FOLD_ == 1, "offset passes use min-tracked folds");
 };
 // The basis form: the plain (8, 4) configuration — its accumulators, every MAC
-// group scalar-counted, row 0 as multiply-adds, min-tracked folds — with the
-// flag set.  A derived type, so that no Cfg<...> instantiation is renamed.
+// group scalar-counted — with the flag set.
 // FILT 1: the ids whose lazy chain is wrong are found by the table of
 // basis_filter.h, once per trip of four ids; 0: by the minimum of each id's
 // eight products (knob u32_basis = 2, kept for comparison).
-template <int PRIO_, int FILT_ = 1>
-struct CfgBasis : Cfg<8, 4, 8, 1, 1, false, false, 0, false, PRIO_> {
+template <bool PRIO_, int FILT_ = 1>
+struct CfgBasis : Cfg<8, 4, 8, PRIO_> {
     static constexpr bool BASIS = true;
     static constexpr bool FILT = FILT_ != 0;
-    static_assert(PRIO_ == 0 || PRIO_ == 4, "basis form: no priority change, or the product's two levels");
 };
 
 template <int NB, int NA, int ROWS = NA - 1>
 struct Acc {
-    uint32_t lo0[NB];         // a = 0 row (ROW0 == 0): sum of B_b mod 2^32
-    uint32_t c0[NB];          // ... its wraps (lane count, or wave total if scalar)
-    uint64_t r0[NB];          // a = 0 row (ROW0 == 1): sum of B_b, 64-bit
+    uint64_t r0[NB];          // a = 0 row: sum of B_b, 64-bit
     uint64_t m[ROWS][NB];     // MAC rows: sum of A_a * B_b mod 2^64
     uint32_t c[ROWS][NB];     // ... its wraps (lane count, or wave total if scalar)
 };
@@ -327,7 +247,7 @@ struct Acc {
 // has no sum row: its MAC rows start at 0)
 template <class C>
 __host__ __device__ constexpr bool scalar_group(int row, int b) {
-    return b / 4 * 4 + 4 <= C::NB && (row > 0 || C::ROW0 == 0 || C::OFF) && row * (C::NB / 4) + b / 4 < C::SG;
+    return b / 4 * 4 + 4 <= C::NB && (row > 0 || C::OFF) && row * (C::NB / 4) + b / 4 < C::SG;
 }
 
 // x^(NB*q) from xn = x^NB by square-and-multiply over the (wave-uniform) q >= 1
@@ -549,7 +469,7 @@ __device__ __forceinline__ uint32_t filter_diff(uint32_t id) {
 
 // powers of one id; returns a value below WRAP_BELOW if a lazy fold may have
 // wrapped (the caller then recomputes exactly): the minimum of the products
-// where folds are min-tracked.  The comparison is the caller's, so that it can
+// (a wrapped fold leaves a value < 25, field.h).  The comparison is the caller's, so that it can
 // place an instruction between the chain's statement and the v_cmp that reads
 // its result (hipcc pads one s_nop there otherwise).
 // OFF: A[a] = x^(base + a*NB).
@@ -575,18 +495,10 @@ __device__ __forceinline__ uint32_t powers(uint32_t id, uint32_t (&B)[C::NB], ui
         for (int a = 1; a < NA; ++a) A[a] = mulfold32_min(A[a - 1], xn, mn);
         if constexpr ((C::XC & 2) != 0) *xnext = mulfold32_min(A[NA - 1], xn, mn);
         return mn;
-    } else if constexpr (C::FOLD == 0) {
-        uint32_t wrapped = 0;
-#pragma unroll
-        for (int b = 1; b < NB; ++b) B[b] = mulfold32_fast(B[b - 1], B[0], wrapped);
-        A[0] = B[NB - 1];
-#pragma unroll
-        for (int a = 1; a < NA - 1; ++a) A[a] = mulfold32_fast(A[a - 1], A[0], wrapped);
-        return wrapped ? 0u : 0xFFFFFFFFu;
     } else {
         // giants after x^NB, and the next pass's x^(NB NA) as one more of them
         constexpr int NG = NA - 2 + ((C::XC & 2) != 0 ? 1 : 0);
-        if constexpr (!C::TREE && LazyChain<NB, NG>::fused) {
+        if constexpr (LazyChain<NB, NG>::fused) {
             uint32_t G[NG ? NG : 1];
             const uint32_t mn = LazyChain<NB, NG>::run(id, B, G);
             A[0] = B[NB - 1];
@@ -596,17 +508,8 @@ __device__ __forceinline__ uint32_t powers(uint32_t id, uint32_t (&B)[C::NB], ui
             return mn;
         }
         uint32_t mn = 0xFFFFFFFFu;
-        if constexpr (C::TREE) {
 #pragma unroll
-            for (int b = 1; b < NB; ++b) {   // B[b] = x^(b+1) = x^h * x^(b+1-h)
-                const int h = 1 << (31 - __builtin_clz((unsigned)(b + 1) - 1u));
-                B[b] = (b + 1) == 2 * h ? mulfold32_min(B[h - 1], B[h - 1], mn)
-                                        : mulfold32_min(B[h - 1], B[b - h], mn);
-            }
-        } else {
-#pragma unroll
-            for (int b = 1; b < NB; ++b) B[b] = mulfold32_min(B[b - 1], B[0], mn);
-        }
+        for (int b = 1; b < NB; ++b) B[b] = mulfold32_min(B[b - 1], B[0], mn);
         A[0] = B[NB - 1];
 #pragma unroll
         for (int a = 1; a < NA - 1; ++a) A[a] = mulfold32_min(A[a - 1], A[0], mn);
@@ -640,46 +543,17 @@ template <class C>
 __device__ __forceinline__ void accumulate(Acc<C::NB, C::NA, C::ROWS> &S, const uint32_t (&B)[C::NB],
                                            const uint32_t (&A)[C::ROWS]) {
     constexpr int NB = C::NB;
-    auto row0 = [&]() {
-    #pragma unroll
+    if constexpr (!C::OFF) {   // the a = 0 sum row (an offset pass has none)
+#pragma unroll
         for (int b = 0; b + 4 <= NB; b += 4) {
-            if constexpr (C::OFF) break;   // no sum row in an offset pass
-            const bool s0 = (b / 4) % 2 == 0;
-            if constexpr (C::ROW0 == 1) {
-                if (s0) row4m<0>(S.r0[b], S.r0[b + 1], S.r0[b + 2], S.r0[b + 3], B[b], B[b + 1], B[b + 2], B[b + 3]);
-                else row4m<1>(S.r0[b], S.r0[b + 1], S.r0[b + 2], S.r0[b + 3], B[b], B[b + 1], B[b + 2], B[b + 3]);
-            } else if (scalar_group<C>(0, b)) {
-                if (s0)
-                    add4s<0>(S.lo0[b], S.lo0[b + 1], S.lo0[b + 2], S.lo0[b + 3], S.c0[b], S.c0[b + 1], S.c0[b + 2],
-                             S.c0[b + 3], B[b], B[b + 1], B[b + 2], B[b + 3]);
-                else
-                    add4s<1>(S.lo0[b], S.lo0[b + 1], S.lo0[b + 2], S.lo0[b + 3], S.c0[b], S.c0[b + 1], S.c0[b + 2],
-                             S.c0[b + 3], B[b], B[b + 1], B[b + 2], B[b + 3]);
-            } else {
-                if (s0)
-                    add4v<0>(S.lo0[b], S.lo0[b + 1], S.lo0[b + 2], S.lo0[b + 3], S.c0[b], S.c0[b + 1], S.c0[b + 2],
-                             S.c0[b + 3], B[b], B[b + 1], B[b + 2], B[b + 3]);
-                else
-                    add4v<1>(S.lo0[b], S.lo0[b + 1], S.lo0[b + 2], S.lo0[b + 3], S.c0[b], S.c0[b + 1], S.c0[b + 2],
-                             S.c0[b + 3], B[b], B[b + 1], B[b + 2], B[b + 3]);
-            }
+            if ((b / 4) % 2 == 0) row4m<0>(S.r0[b], S.r0[b + 1], S.r0[b + 2], S.r0[b + 3], B[b], B[b + 1], B[b + 2], B[b + 3]);
+            else row4m<1>(S.r0[b], S.r0[b + 1], S.r0[b + 2], S.r0[b + 3], B[b], B[b + 1], B[b + 2], B[b + 3]);
         }
-        if constexpr (NB % 4 == 2 && !C::OFF) {
-            if constexpr (C::ROW0 == 1) row2m(S.r0[NB - 2], S.r0[NB - 1], B[NB - 2], B[NB - 1]);
-            else add2v(S.lo0[NB - 2], S.lo0[NB - 1], S.c0[NB - 2], S.c0[NB - 1], B[NB - 2], B[NB - 1]);
-        }
-    };
-    if constexpr (C::PRIO != 7) row0();
-    if constexpr (C::PRIO == 3) __builtin_amdgcn_s_setprio(1);   // (measurements: the MAC rows only)
-    if constexpr (C::PRIO == 4) __builtin_amdgcn_s_setprio(2);   // row 0 at 1, the MAC rows at 2
-    if constexpr (C::PRIO == 6) __builtin_amdgcn_s_setprio(2);   // (measurements: row 0 at 3, the rows at 2)
+        if constexpr (NB % 4 == 2) row2m(S.r0[NB - 2], S.r0[NB - 1], B[NB - 2], B[NB - 1]);
+    }
+    if constexpr (C::PRIO) __builtin_amdgcn_s_setprio(2);   // row 0 at 1, the MAC rows at 2
 #pragma unroll
     for (int a = 0; a < C::ROWS; ++a) {
-        // (measurements) 5: row 0 at 1, MAC row a at min(3, 2 + a)
-        if constexpr (C::PRIO == 5) {
-            if (a == 0) __builtin_amdgcn_s_setprio(2);
-            else __builtin_amdgcn_s_setprio(3);
-        }
 #pragma unroll
         for (int b = 0; b + 4 <= NB; b += 4) {
             const int g = (a + C::ROW1) * (NB / 4) + b / 4;   // group index: parity picks the SGPR set
@@ -701,10 +575,6 @@ __device__ __forceinline__ void accumulate(Acc<C::NB, C::NA, C::ROWS> &S, const 
         }
         if constexpr (NB % 4 == 2)
             mac2v(S.m[a][NB - 2], S.m[a][NB - 1], S.c[a][NB - 2], S.c[a][NB - 1], A[a], B[NB - 2], B[NB - 1]);
-    }
-    if constexpr (C::PRIO == 7) {   // (measurements: the MAC rows first at 2, then row 0 at 1)
-        __builtin_amdgcn_s_setprio(1);
-        row0();
     }
 }
 
@@ -733,7 +603,7 @@ __device__ __forceinline__ void accumulate_basis(Acc<8, 4, 3> &S, const uint32_t
     static_assert(basis32::ND == 8 && basis32::NM == 24, "two direct groups, six pair groups");
     basis_direct4<C, 0>(S, V);
     basis_direct4<C, 1>(S, V);
-    if constexpr (C::PRIO == 4) __builtin_amdgcn_s_setprio(2);
+    if constexpr (C::PRIO) __builtin_amdgcn_s_setprio(2);
     basis_mac4<C, 0>(S, V);
     basis_mac4<C, 1>(S, V);
     basis_mac4<C, 2>(S, V);
@@ -747,16 +617,12 @@ constexpr int basis_slot_power(int a, int b) {
 }
 
 // wave priority around an id's accumulation (Cfg PRIO; accumulate raises it
-// further before the MAC rows for PRIO 3-6)
+// further before the MAC rows)
 template <class C> __device__ __forceinline__ void prio_enter() {
-    if constexpr (C::PRIO == 1 || C::PRIO == 4 || C::PRIO == 5) __builtin_amdgcn_s_setprio(1);
-    if constexpr (C::PRIO == 6) __builtin_amdgcn_s_setprio(3);
-    if constexpr (C::PRIO == 7) __builtin_amdgcn_s_setprio(2);
-    if constexpr (C::PRIO == 2) __builtin_amdgcn_s_setprio(0);
+    if constexpr (C::PRIO) __builtin_amdgcn_s_setprio(1);
 }
 template <class C> __device__ __forceinline__ void prio_exit() {
-    if constexpr (C::PRIO == 1 || C::PRIO >= 3) __builtin_amdgcn_s_setprio(0);
-    if constexpr (C::PRIO == 2) __builtin_amdgcn_s_setprio(1);
+    if constexpr (C::PRIO) __builtin_amdgcn_s_setprio(0);
 }
 
 // The filtered basis form (CfgBasis FILT).  A trip whose filter test found
@@ -771,7 +637,7 @@ __device__ __forceinline__ void basis_one_lazy(Acc<8, 4, 3> &S, uint32_t id) {
     uint32_t V[basis32::NE];
     basis_chain(id, V);
     prio_enter<C>();
-    if constexpr (C::PRIO != 0) __builtin_amdgcn_sched_barrier(0);
+    if constexpr (C::PRIO) __builtin_amdgcn_sched_barrier(0);
     accumulate_basis<C>(S, V);
     prio_exit<C>();
 }
@@ -801,7 +667,7 @@ __device__ __forceinline__ void one(Acc<C::NB, C::NA, C::ROWS> &S, uint32_t id, 
         uint32_t V[basis32::NE];
         const uint32_t mn = basis_chain_min(id, V);
         prio_enter<C>();
-        if constexpr (C::PRIO != 0) __builtin_amdgcn_sched_barrier(0);
+        if constexpr (C::PRIO) __builtin_amdgcn_sched_barrier(0);
         const bool w = mn < WRAP_BELOW;
         if (__builtin_expect(__any(w), 0)) {
             if (w) basis32::chain_exact(id, V);
@@ -816,30 +682,12 @@ __device__ __forceinline__ void one(Acc<C::NB, C::NA, C::ROWS> &S, uint32_t id, 
     // its minimum, where an s_nop would stand otherwise (the rare redo runs at
     // the accumulation's priority)
     prio_enter<C>();
-    if constexpr (C::PRIO != 0) __builtin_amdgcn_sched_barrier(0);
+    if constexpr (C::PRIO) __builtin_amdgcn_sched_barrier(0);
     const bool w = mn < WRAP_BELOW;
     if (__builtin_expect(__any(w), 0)) {
         if (w) powers_exact<C>(B, A, base, xb, xnext);
     }
     accumulate<C>(S, B, A);
-    prio_exit<C>();
-}
-
-// two ids at once: their power chains are independent straight-line code, so
-// the compiler interleaves them (ILP for the dependent modmul chains)
-template <class C>
-__device__ __forceinline__ void two(Acc<C::NB, C::NA, C::ROWS> &S, uint32_t id0, uint32_t id1) {
-    static_assert(!C::OFF, "pairs: plain passes only");
-    uint32_t B0[C::NB], A0[C::ROWS], B1[C::NB], A1[C::ROWS];
-    const bool w0 = powers<C>(id0, B0, A0) < WRAP_BELOW;
-    const bool w1 = powers<C>(id1, B1, A1) < WRAP_BELOW;
-    if (__builtin_expect(__any(w0 | w1), 0)) {
-        if (w0) powers_exact<C>(B0, A0);
-        if (w1) powers_exact<C>(B1, A1);
-    }
-    prio_enter<C>();
-    accumulate<C>(S, B0, A0);
-    accumulate<C>(S, B1, A1);
     prio_exit<C>();
 }
 
@@ -861,9 +709,6 @@ __device__ __forceinline__ void four(Acc<C::NB, C::NA, C::ROWS> &S, uint4 w, uin
         basis_one_lazy<C>(S, w.y);
         basis_one_lazy<C>(S, w.z);
         basis_one_lazy<C>(S, w.w);
-    } else if constexpr (C::PAIR) {
-        two<C>(S, w.x, w.y);
-        two<C>(S, w.z, w.w);
     } else {
         uint4 t = make_uint4(0, 0, 0, 0);
         one<C>(S, w.x, base, xb.x, &t.x);
@@ -888,18 +733,15 @@ __device__ __forceinline__ void finish(const Acc<C::NB, C::NA, C::ROWS> &S, uint
     for (int a = 0; a < NA; ++a) {
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
-            // value = lo + c * W with W = 2^32 == 5 (a = 0) or 2^64 == 25 (a > 0);
-            // a scalar-counted c is the wave's total, added once (by lane 0)
-            const bool sc = scalar_group<C>(a, b);
-            const uint32_t c = C::OFF ? S.c[a][b] : a == 0 ? S.c0[b] : S.c[a - C::ROW1][b];
-            const uint32_t cl = sc ? (lane == 0 ? c : 0u) : c;
+            // the sum row's value is its 64-bit sum; a MAC row's is m + c * 2^64
+            // with 2^64 == 25; a scalar-counted c is the wave's total, added
+            // once (by lane 0)
             uint64_t x;
-            if (C::OFF) {
-                x = (uint64_t)fold64_32(S.m[a][b]) + fold64_32((uint64_t)cl * 25u);
-            } else if (a == 0) {
-                if constexpr (C::ROW0 == 1) x = S.r0[b];
-                else x = (uint64_t)S.lo0[b] + (uint64_t)cl * 5u;                      // < 6*2^32
+            if (!C::OFF && a == 0) {
+                x = S.r0[b];
             } else {
+                const uint32_t c = S.c[a - C::ROW1][b];
+                const uint32_t cl = scalar_group<C>(a, b) ? (lane == 0 ? c : 0u) : c;
                 x = (uint64_t)fold64_32(S.m[a - C::ROW1][b]) + fold64_32((uint64_t)cl * 25u);
             }
             x = fold64_32(x);                                                         // < 2^32
@@ -937,8 +779,6 @@ template <class C>
 __device__ __forceinline__ void clear(Acc<C::NB, C::NA, C::ROWS> &S) {
 #pragma unroll
     for (int b = 0; b < C::NB; ++b) {
-        S.lo0[b] = 0;
-        S.c0[b] = 0;
         S.r0[b] = 0;
 #pragma unroll
         for (int a = 0; a < C::ROWS; ++a) { S.m[a][b] = 0; S.c[a][b] = 0; }

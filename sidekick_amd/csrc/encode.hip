@@ -14,7 +14,7 @@
 //     4.47 SIMD-cycles of VALU issue per id (the algorithmic anchor,
 //     tools/issue_model.py); the kernel issues 1.19 VALU + 0.76 SALU
 //     wave-instructions per id, each id's MAC phase at raised wave priority
-//     (s_setprio, knob bsgs_prio).  Streams below 2^32 ids take the dynamic
+//     (s_setprio, bsgs.h Cfg PRIO).  Streams below 2^32 ids take the dynamic
 //     form k_encode_u32_bsgs_dyn (knob enc_dyn): one round of resident
 //     workgroups whose waves claim 4 096-id chunks from eight counters; only
 //     the wave that finds the chunks exhausted at counter 0 runs masked trips
@@ -32,7 +32,7 @@
 //     are looked up in an LDS table once per trip (basis_filter.h).
 //     u32_basis = 2 finds them by the minimum of each id's products instead;
 //     u32_basis = 0 and the all-VALU fallback take the grid.
-//   * 14 <= t <= 80 (u64) — k_encode_u64_bsgs<NA,SG,F> (bsgs64.h): the
+//   * 14 <= t <= 80 (u64) — k_encode_u64_bsgs<NA,SG> (bsgs64.h): the
 //     same split with the babies/giants of a 256-id tile shared through LDS,
 //     each wave owning two babies' MAC rows (paired, at raised priority).
 //   * t > 80 — passes of the BSGS kernels (offset giants x^(base + 8a)).
@@ -54,17 +54,6 @@
 #include "field.h"
 #include "bsgs.h"
 #include "bsgs64.h"
-
-// scalar-counted wrap groups of the t = 25..32 BSGS kernel (tools/tune_bsgs.hip)
-#ifndef QK_BSGS_SG_T32
-#define QK_BSGS_SG_T32 8
-#endif
-#ifndef QK_BSGS_ROW0
-#define QK_BSGS_ROW0 1
-#endif
-#ifndef QK_BSGS_FOLD
-#define QK_BSGS_FOLD 1
-#endif
 
 namespace qk {
 
@@ -104,28 +93,26 @@ __device__ __forceinline__ void chain32x4(uint64_t (&acc)[K], uint4 w) {
 // ---- baby-step / giant-step encode, the shapes of QK_U32_SHAPES below (bsgs.h)
 // waves per SIMD the register budget is sized for (tools/tune_bsgs.hip: 5 for
 // (8,4) beat 4 by 2-3 %; its three spilled VGPRs live outside the loop)
-// PRIO (knob bsgs_prio): wave priority over each id's accumulation — row 0
-// at 1, the MAC rows at 2, the powers at 0 (bsgs.h Cfg PRIO 4; t = 32: 2.60 /
-// 2.67 vs 2.66 / 2.73 ms for the MAC phase at 1, vs 2.77 ms for none,
+// Every encode kernel runs each id's accumulation at raised wave priority —
+// row 0 at 1, the MAC rows at 2, the powers at 0 (bsgs.h Cfg PRIO; t = 32:
+// 2.60 / 2.67 vs 2.66 / 2.73 ms for the MAC phase at 1, vs 2.77 ms for none,
 // profiles/r04/prio/tune_bsgs_prio_levels*.json)
-template <int NB, int NA, int SG, int PRIO = 1>
+template <int NB, int NA, int SG>
 __global__ __launch_bounds__(BLOCK, (NB * NA == 32 ? 5 : NB * NA > 64 ? 2 : NB * NA > 40 ? 3 : 4)) void k_encode_u32_bsgs(const uint32_t *__restrict__ ids,
                                                                                   uint64_t n, uint32_t head,
                                                                                   uint32_t T,
                                                                                   uint64_t *__restrict__ partials) {
-    bsgs::body<bsgs::Cfg<NB, NA, SG, QK_BSGS_ROW0, QK_BSGS_FOLD, false, false, 0, false, PRIO ? 4 : 0>>(ids, n, head,
-                                                                                                        T, partials);
+    bsgs::body<bsgs::Cfg<NB, NA, SG, true>>(ids, n, head, T, partials);
 }
 
 // The same with the ids handed out dynamically (bsgs.h body_dyn): the waves
 // claim chunks of 64 x DYN_CH 16-byte groups from the counter `ctr`, whose
 // value before this launch is `cbase`.
-template <int NB, int NA, int SG, int PRIO = 1>
+template <int NB, int NA, int SG>
 __global__ __launch_bounds__(BLOCK, (NB * NA == 32 ? 5 : NB * NA > 64 ? 2 : NB * NA > 40 ? 3 : 4)) void k_encode_u32_bsgs_dyn(
     const uint32_t *__restrict__ ids, uint64_t n, uint32_t head, uint32_t T, uint64_t *__restrict__ partials,
     const bsgs::DynArgs da) {
-    bsgs::body_dyn<bsgs::Cfg<NB, NA, SG, QK_BSGS_ROW0, QK_BSGS_FOLD, false, false, 0, false, PRIO ? 4 : 0>>(
-        ids, n, head, T, partials, da);
+    bsgs::body_dyn<bsgs::Cfg<NB, NA, SG, true>>(ids, n, head, T, partials, da);
 }
 
 // t = 31..32 from the nine-power basis (basis32.h, bsgs.h CfgBasis; knob
@@ -133,43 +120,41 @@ __global__ __launch_bounds__(BLOCK, (NB * NA == 32 ? 5 : NB * NA > 64 ? 2 : NB *
 // accumulators, wrap counting and priorities.  Static and dynamic form.
 // FILT 1: wrong ids by the table of basis_filter.h (16 KiB of LDS per
 // workgroup); 0: by the minimum of the products (knob u32_basis = 2).
-template <int PRIO = 1, int FILT = 1>
+template <int FILT = 1>
 __global__ __launch_bounds__(BLOCK, 5) void k_encode_u32_basis(const uint32_t *__restrict__ ids, uint64_t n,
                                                               uint32_t head, uint32_t T,
                                                               uint64_t *__restrict__ partials) {
-    bsgs::body<bsgs::CfgBasis<PRIO ? 4 : 0, FILT>>(ids, n, head, T, partials);
+    bsgs::body<bsgs::CfgBasis<true, FILT>>(ids, n, head, T, partials);
 }
-template <int PRIO = 1, int FILT = 1>
+template <int FILT = 1>
 __global__ __launch_bounds__(BLOCK, 5) void k_encode_u32_basis_dyn(const uint32_t *__restrict__ ids, uint64_t n,
                                                                   uint32_t head, uint32_t T,
                                                                   uint64_t *__restrict__ partials,
                                                                   const bsgs::DynArgs da) {
-    bsgs::body_dyn<bsgs::CfgBasis<PRIO ? 4 : 0, FILT>>(ids, n, head, T, partials, da);
+    bsgs::body_dyn<bsgs::CfgBasis<true, FILT>>(ids, n, head, T, partials, da);
 }
 
 // Pass 0 of a multi-pass encode (powers 1..80) that also writes x^80 per id
 // for pass 1 (the x^base cache, enc_passes_chunk)
-template <int SG, int PRIO = 1>
+template <int SG>
 __global__ __launch_bounds__(BLOCK, 2) void k_encode_u32_bsgs_x80(const uint32_t *__restrict__ ids, uint64_t n,
                                                                  uint32_t head, uint32_t T,
                                                                  uint64_t *__restrict__ partials,
                                                                  const uint32_t *xin,
                                                                  uint32_t *xout) {
     (void)xin;
-    bsgs::body<bsgs::Cfg<8, 10, SG, 1, 1, false, false, 2, false, PRIO ? 4 : 0>>(ids, n, head, T, partials, 0, nullptr,
-                                                                                 xout);
+    bsgs::body<bsgs::Cfg<8, 10, SG, true, 2>>(ids, n, head, T, partials, 0, nullptr, xout);
 }
 
 // Offset pass for thresholds > 80 (several passes over the ids): powers
 // base+1 .. base+8*NA with giants x^(base + 8a), a = 0..NA-1 (bsgs.h OFF).
 // XC: x^base from the previous pass's per-id cache (bit 0) / x^(base + 8 NA)
 // to the next pass's (bit 1) instead of square-and-multiply per pass.
-template <int NA, int SG, int XC = 0, int PRIO = 1>
+template <int NA, int SG, int XC = 0>
 __global__ __launch_bounds__(BLOCK, (NA > 6 ? 2 : NA > 5 ? 3 : 4)) void k_encode_u32_bsgs_off(
     const uint32_t *__restrict__ ids, uint64_t n, uint32_t head, uint32_t T, uint32_t base,
     uint64_t *__restrict__ partials, const uint32_t *xin, uint32_t *xout) {
-    bsgs::body<bsgs::Cfg<8, NA, SG, 1, 1, false, true, XC, false, PRIO ? 4 : 0>>(ids, n, head, T, partials, base, xin,
-                                                                                 xout);
+    bsgs::body<bsgs::Cfg<8, NA, SG, true, XC, true>>(ids, n, head, T, partials, base, xin, xout);
 }
 
 // Reduce per-lane accumulators to one partial per (power, block).
@@ -533,47 +518,44 @@ __global__ __launch_bounds__(BLOCK) void k_finalize_u64(const uint64_t *__restri
 
 // u64 baby-step / giant-step (bsgs64.h): 256-id tiles, babies and giants
 // shared through LDS, the MAC powers split over the 4 waves.  The babies'
-// B * 2^32 are recomputed by their owner wave instead of stored (BSH) and x^8
+// B * 2^32 are recomputed by their owner wave instead of stored and x^8
 // is read from baby 8: 32 KB of LDS per workgroup at t = 80, 4 per CU
 // (tools/tune_u64.hip: 24.1 vs 25.6 ms per 1e9 ids with 50 KB at 3 per CU).
-// The first SG MACs of a wave's tile count their carries on the scalar unit.
-// F (knob bsgs64_prio): 1 — wave priority in the MAC step (the row-0 sums
-// at 1, the MACs at 2: bsgs64.h PRIO 3, ~1 % over one level) and, with two
-// babies per wave, the two MACs of a giant row issued as one interleaved
-// block (MODE 3); 0 — the round-3 form (MODE 0, no priority changes)
-template <int NA, int SG, int F = 1>
+// The first SG MACs of a wave's tile count their carries on the scalar unit;
+// with two babies per wave the two MACs of a giant row are issued as one
+// interleaved block.  The MAC step runs at raised wave priority (the row-0
+// sums at 1, the MACs at 2: ~1 % over one level).
+template <int NA, int SG>
 __global__ __launch_bounds__(bsgs64::BLOCK, 4) void k_encode_u64_bsgs(const uint64_t *__restrict__ ids, uint64_t n,
                                                                       uint32_t head, uint32_t T,
                                                                       uint64_t *__restrict__ partials) {
     (void)head;
-    bsgs64::body<NA, F ? 3 : 0, SG, 0, 0, false, true, 1, 0, bsgs64::NB, F ? 3 : 0>(ids, n, T, partials);
+    bsgs64::body<bsgs64::Cfg<NA, 8, SG>>(ids, n, T, partials);
 }
 
 // the same with four babies per id (one per wave) and NA giant rows of 4
 // powers: t <= 40 (bsgs64.h NBT)
-template <int NA, int F = 1>
+template <int NA>
 __global__ __launch_bounds__(bsgs64::BLOCK, 4) void k_encode_u64_bsgs4(const uint64_t *__restrict__ ids, uint64_t n,
                                                                        uint32_t head, uint32_t T,
                                                                        uint64_t *__restrict__ partials) {
     (void)head;
-    bsgs64::body<NA, 0, 16, 0, 0, false, true, 1, 0, 4, F ? 3 : 0>(ids, n, T, partials);
+    bsgs64::body<bsgs64::Cfg<NA, 4, 16>>(ids, n, T, partials);
 }
 
 // Pass 0 of a u64 multi-pass encode that also writes x^80 per id for pass 1
-template <int F = 1>
 __global__ __launch_bounds__(bsgs64::BLOCK, 4) void k_encode_u64_bsgs_x80(const uint64_t *__restrict__ ids,
                                                                           uint64_t n, uint32_t head, uint32_t T,
                                                                           uint64_t *__restrict__ partials,
                                                                           uint64_t *xout) {
     (void)head;
-    bsgs64::body<10, F ? 3 : 0, 16, 0, 0, false, true, 1, 2, bsgs64::NB, F ? 3 : 0>(ids, n, T, partials, 0, nullptr,
-                                                                                 xout);
+    bsgs64::body<bsgs64::Cfg<10, 8, 16, 2>>(ids, n, T, partials, 0, nullptr, xout);
 }
 
 // Offset pass for u64 thresholds > 80: powers base+1 .. base+8NA with giants
 // x^(base + 8a) (bsgs64.h OFF); the ids are read once per pass.
 // XC: the per-id x^base cache between passes (bsgs64.h)
-template <int NA, int XC = 0, int F = 1>
+template <int NA, int XC = 0>
 __global__ __launch_bounds__(bsgs64::BLOCK, 4) void k_encode_u64_bsgs_off(const uint64_t *__restrict__ ids,
                                                                           uint64_t n, uint32_t head, uint32_t T,
                                                                           uint32_t base,
@@ -581,8 +563,7 @@ __global__ __launch_bounds__(bsgs64::BLOCK, 4) void k_encode_u64_bsgs_off(const 
                                                                           const uint64_t *xin,
                                                                           uint64_t *xout) {
     (void)head;
-    bsgs64::body<NA, F ? 3 : 0, 16, 0, 0, true, true, 1, XC, bsgs64::NB, F ? 3 : 0>(ids, n, T, partials, base, xin,
-                                                                                     xout);
+    bsgs64::body<bsgs64::Cfg<NA, 8, 16, XC, true>>(ids, n, T, partials, base, xin, xout);
 }
 
 // ------------------------------------------------------------- dispatch
@@ -764,7 +745,7 @@ static int enc_passes_chunk(qk_ctx *ctx, const uint32_t *ids, size_t n, uint32_t
         // x^(base + 8 NA) to it (bit 1)
         auto off = [&](auto na, auto x) {
             constexpr int NA = decltype(na)::value, XC = decltype(x)::value;
-            auto kern = k_encode_u32_bsgs_off<NA, 2 * NA, XC, 1>;
+            auto kern = k_encode_u32_bsgs_off<NA, 2 * NA, XC>;
             return run_pass(kern, 8 * NA, [&](uint32_t nb, uint64_t *partials) {
                 launch(kern, nb, s, ids, (uint64_t)n, head, Tp, base, partials, (const uint32_t *)(XC & 1 ? xc : nullptr),
                        XC & 2 ? xc : nullptr);
@@ -774,12 +755,12 @@ static int enc_passes_chunk(qk_ctx *ctx, const uint32_t *ids, size_t n, uint32_t
         const int xcm = !xc ? 0 : (pass > 0 ? 1 : 0) | (pass < npass ? 2 : 0);
         int rc;
         if (base == 0 && xc) {
-            auto kern = k_encode_u32_bsgs_x80<16, 1>;
+            auto kern = k_encode_u32_bsgs_x80<16>;
             rc = run_pass(kern, 80, [&](uint32_t nb, uint64_t *partials) {
                 launch(kern, nb, s, ids, (uint64_t)n, head, Tp, partials, (const uint32_t *)nullptr, xc);
             });
         } else if (base == 0) {
-            auto kern = k_encode_u32_bsgs<8, 10, 16, 1>;
+            auto kern = k_encode_u32_bsgs<8, 10, 16>;
             rc = run_pass(kern, 80, [&](uint32_t nb, uint64_t *partials) {
                 launch(kern, nb, s, ids, (uint64_t)n, head, Tp, partials);
             });
@@ -825,9 +806,9 @@ static int enc_passes_chunk(qk_ctx *ctx, const uint64_t *ids, size_t n, uint32_t
                              finalize_to(Tp, ids, n, out + 2 * base, base == 0 ? out + 2 * T : nullptr, acc, s));
     };
     // pass 0: powers 1..80 (+ x^80 per id for pass 1 when the cache is on)
-    if (int rc = run_pass(k_encode_u64_bsgs<10, 14, 1>, 10, 80, 0, [&](uint32_t nb, uint64_t *partials) {
-            if (xc) launch(k_encode_u64_bsgs_x80<1>, nb, s, ids, (uint64_t)n, head, 80u, partials, xc);
-            else launch(k_encode_u64_bsgs<10, 14, 1>, nb, s, ids, (uint64_t)n, head, 80u, partials);
+    if (int rc = run_pass(k_encode_u64_bsgs<10, 14>, 10, 80, 0, [&](uint32_t nb, uint64_t *partials) {
+            if (xc) launch(k_encode_u64_bsgs_x80, nb, s, ids, (uint64_t)n, head, 80u, partials, xc);
+            else launch(k_encode_u64_bsgs<10, 14>, nb, s, ids, (uint64_t)n, head, 80u, partials);
         }))
         return rc;
     uint32_t pass = 1;
@@ -836,7 +817,7 @@ static int enc_passes_chunk(qk_ctx *ctx, const uint64_t *ids, size_t n, uint32_t
         // an offset pass of NA giant rows; XC: the cache read (bit 0) and written (bit 1)
         auto off = [&](auto na, auto x) {
             constexpr int NA = decltype(na)::value, XC = decltype(x)::value;
-            auto kern = k_encode_u64_bsgs_off<NA, XC, 1>;
+            auto kern = k_encode_u64_bsgs_off<NA, XC>;
             uint64_t *c = XC ? xc : nullptr;
             return run_pass(kern, NA, Tp, base, [&](uint32_t nb, uint64_t *partials) {
                 launch(kern, nb, s, ids, (uint64_t)n, head, Tp, base, partials, (const uint64_t *)c, c);
@@ -921,7 +902,7 @@ static int enc_chain(uint32_t T, ints<Gs...> gs, F &&gk) {
     X(21, 24, 4, 6, 6)             \
     X(25, 28, 4, 7, 7)             \
     X(29, 30, 6, 5, 5)             \
-    X(31, 32, 8, 4, QK_BSGS_SG_T32) \
+    X(31, 32, 8, 4, 8)             \
     X(33, 36, 6, 6, 6)             \
     X(37, 40, 8, 5, 10)            \
     X(41, 42, 6, 7, 7)             \
@@ -951,21 +932,21 @@ static int enc32(qk_ctx *ctx, const uint32_t *ids, size_t n, uint32_t T, uint64_
     // streams keep the static split.
     const bool dyn = ctx->knobs.enc_dyn != 0 && n < (1ull << 32);
 #define QK_BSGS_STATIC(NB_, NA_, G_)                                                                      \
-    run_encode(ctx, k_encode_u32_bsgs<NB_, NA_, G_, 1>, NB_ * NA_, ids, n, head, T, (n + 3) / 4, BLOCK, out, acc, s, \
+    run_encode(ctx, k_encode_u32_bsgs<NB_, NA_, G_>, NB_ * NA_, ids, n, head, T, (n + 3) / 4, BLOCK, out, acc, s, \
                NB_ * NA_ > 48 ? 1 : 0)
 #define QK_BSGS(NB_, NA_, G_)                                                                             \
-    (dyn ? run_encode_dyn(ctx, k_encode_u32_bsgs_dyn<NB_, NA_, G_, 1>, NB_ * NA_, ids, n, head, T, out, acc, s) \
+    (dyn ? run_encode_dyn(ctx, k_encode_u32_bsgs_dyn<NB_, NA_, G_>, NB_ * NA_, ids, n, head, T, out, acc, s) \
          : QK_BSGS_STATIC(NB_, NA_, G_))
 #define QK_BSGS_ROW(LO_, HI_, NB_, NA_, G_) \
     if (T >= LO_ && T <= HI_) return QK_BSGS(NB_, NA_, G_);
     if (sc_ok) {
         if (T >= 31 && T <= 32 && ctx->knobs.u32_basis == 1)   // the nine-power basis (basis32.h), ids filtered
-            return dyn ? run_encode_dyn(ctx, k_encode_u32_basis_dyn<1, 1>, 32, ids, n, head, T, out, acc, s)
-                       : run_encode(ctx, k_encode_u32_basis<1, 1>, 32, ids, n, head, T, (n + 3) / 4, BLOCK, out, acc,
+            return dyn ? run_encode_dyn(ctx, k_encode_u32_basis_dyn<1>, 32, ids, n, head, T, out, acc, s)
+                       : run_encode(ctx, k_encode_u32_basis<1>, 32, ids, n, head, T, (n + 3) / 4, BLOCK, out, acc,
                                     s, 0);
         if (T >= 31 && T <= 32 && ctx->knobs.u32_basis == 2)   // ... with the minimum tracked per product
-            return dyn ? run_encode_dyn(ctx, k_encode_u32_basis_dyn<1, 0>, 32, ids, n, head, T, out, acc, s)
-                       : run_encode(ctx, k_encode_u32_basis<1, 0>, 32, ids, n, head, T, (n + 3) / 4, BLOCK, out, acc,
+            return dyn ? run_encode_dyn(ctx, k_encode_u32_basis_dyn<0>, 32, ids, n, head, T, out, acc, s)
+                       : run_encode(ctx, k_encode_u32_basis<0>, 32, ids, n, head, T, (n + 3) / 4, BLOCK, out, acc,
                                     s, 0);
         QK_U32_SHAPES(QK_BSGS_ROW)
         if (T > 80) return enc_passes(ctx, ids, n, head, T, out, acc, s);
@@ -1000,7 +981,7 @@ static int enc64(qk_ctx *ctx, const uint64_t *ids, size_t n, uint32_t T, uint64_
     // they save: profiles/r03/shapes/sweep64_tmin_ab.jsonl — 21 before round
     // 3, BSGS +3..9 % at t = 14..20): NA = ceil(T / 8) giant rows; its
     // per-wave 32-bit carry totals need < 2^31 ids per workgroup.  Every form
-    // runs with s_setprio around the MACs and paired MACs (F = 1).
+    // runs with s_setprio around the MACs.
     const uint64_t min_grid64 = ctx->grid_override ? ctx->grid_override : (uint64_t)ctx->num_cus;
     const bool bsgs_ok = n / min_grid64 < (1ull << 30);
     if (T >= 14 && T <= 80 && bsgs_ok) {
@@ -1011,7 +992,7 @@ static int enc64(qk_ctx *ctx, const uint64_t *ids, size_t n, uint32_t T, uint64_
         // 29..32 even, at 37..40 7 % slower: not used)
         const int rc4 = with_int(T <= 36 ? (T + 3) / 4 : 0, ints<4, 5, 7, 9>{}, 1, [&](auto na) {
             constexpr int NA = decltype(na)::value;
-            return run_encode(ctx, k_encode_u64_bsgs4<NA, 1>, 4 * NA, ids, n, head, T, tiles, 1, out, acc, s);
+            return run_encode(ctx, k_encode_u64_bsgs4<NA>, 4 * NA, ids, n, head, T, tiles, 1, out, acc, s);
         });
         if (rc4 <= 0) return rc4;   // 1: no four-baby form at this T (a status is <= 0)
         return with_int((T + 7) / 8, ints<2, 3, 4, 5, 6, 7, 8, 9, 10>{}, QK_E_THRESHOLD, [&](auto na) {
@@ -1019,7 +1000,7 @@ static int enc64(qk_ctx *ctx, const uint64_t *ids, size_t n, uint32_t T, uint64_
             // NA = 10: 14 of the 18 MACs scalar-counted with the paired-MAC form
             // (22.65 vs 23.19 ms at 16, twice, profiles/r04/prio/tune_u64_prio.json)
             constexpr int NA = decltype(na)::value, SG = NA == 10 ? 14 : 16;
-            return run_encode(ctx, k_encode_u64_bsgs<NA, SG, 1>, 8 * NA, ids, n, head, T, tiles, 1, out, acc, s);
+            return run_encode(ctx, k_encode_u64_bsgs<NA, SG>, 8 * NA, ids, n, head, T, tiles, 1, out, acc, s);
         });
     }
     if (T > 80 && bsgs_ok) return enc_passes(ctx, ids, n, head, T, out, acc, s);

@@ -73,7 +73,7 @@ struct NoEncode {};
 // the kernel.
 template <int NA_> struct Shared {
     static constexpr int NA = NA_;
-    using Pw = bsgs::Cfg<8, NA_, 0, 1, 1>;   // the powers (min-tracked lazy folds)
+    using Pw = bsgs::Cfg<8, NA_, 0>;   // the powers (min-tracked lazy folds)
 };
 template <class C> struct IsShared : std::false_type {};
 template <int NA> struct IsShared<Shared<NA>> : std::true_type {};

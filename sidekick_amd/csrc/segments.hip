@@ -72,8 +72,7 @@ __global__ __launch_bounds__(bsgs::BLOCK, (NB * NA == 32 ? 5 : NB * NA > 64 ? 2 
     const uint32_t *p = ids + it.lo;
     const uint32_t head = (uint32_t)(((16u - ((uint32_t)(uintptr_t)p & 15u)) & 15u) >> 2);   // ids to 16-B alignment
     unsigned long long *row = acc_out + (size_t)it.seg * T;
-    bsgs::body_gen<bsgs::Cfg<NB, NA, SG, 1, 1, false, false, 0, false, 0>>(p, it.hi - it.lo, head, T, threadIdx.x,
-                                                                             (uint64_t)bsgs::BLOCK,
+    bsgs::body_gen<bsgs::Cfg<NB, NA, SG>>(p, it.hi - it.lo, head, T, threadIdx.x, (uint64_t)bsgs::BLOCK,
                                           [=](uint32_t m, uint64_t s) {
                                               atomicAdd(&row[m], (unsigned long long)fold64_32(s));
                                           });
@@ -104,11 +103,12 @@ __global__ __launch_bounds__(SG_BLOCK, 4) void k_seg_small(const uint32_t *__res
     if (g >= nseg) return;
     const uint64_t b = offs[g], e = offs[g + 1];
     if (e - b > SMALL_SEG) return;   // a work-item flow
+    // (zeroed here and not by bsgs::clear: through the call the compiler keeps
+    // 2-3 more VGPRs in every shape and spills 6 instead of 2 at (8,4),
+    // profiles/encode_cfg/README.md)
     bsgs::Acc<C::NB, C::NA> S;
 #pragma unroll
     for (int j = 0; j < C::NB; ++j) {
-        S.lo0[j] = 0;
-        S.c0[j] = 0;
         S.r0[j] = 0;
 #pragma unroll
         for (int a = 0; a < C::NA - 1; ++a) { S.m[a][j] = 0; S.c[a][j] = 0; }
@@ -164,9 +164,9 @@ __global__ __launch_bounds__(SG_BLOCK, 4) void k_seg_small(const uint32_t *__res
 int seg_small_launch(uint32_t T, const uint32_t *ids, const uint64_t *d_offs, uint32_t nseg,
                             unsigned long long *acc, const SmallOut &so, hipStream_t s) {
     const dim3 grid((nseg + SG_BLOCK - 1) / SG_BLOCK), block(SG_BLOCK);
-#define QK_SMALL(NB_, NA_)                                                                                         \
-    hipLaunchKernelGGL((k_seg_small<bsgs::Cfg<NB_, NA_, 0, 1, 1, false, false, 0, false, 0>>), grid, block, 0, s, ids, \
-                       d_offs, nseg, T, acc, so.rec, so.rseg, so.lastid)
+#define QK_SMALL(NB_, NA_)                                                                                    \
+    hipLaunchKernelGGL((k_seg_small<bsgs::Cfg<NB_, NA_, 0>>), grid, block, 0, s, ids, d_offs, nseg, T, acc, so.rec, \
+                       so.rseg, so.lastid)
     if (T <= 8) QK_SMALL(4, 2);
     else if (T <= 12) QK_SMALL(4, 3);
     else if (T <= 16) QK_SMALL(4, 4);

@@ -24,8 +24,9 @@ The functions restate, instruction by instruction, bsgs64.h QK_U64_MULV_ASM
 (`mulv`) and `shift32`, encode.hip QK_U64_STEP_ASM / QK_U64_MUL_ASM (`chain`,
 `tmul`) and `vfold64`, field.h `mul64_lazy` / `mad64_lazy`, decode.hip
 `horner64_step` and `is_root64_bsgs`, and the product schedules of
-bsgs64::body (TR = 0, BSH) and of enc64 / enc_passes_chunk.  FIX holds the
-constants of the fix-ups, so a test can zero one and see which sums change.
+bsgs64::body (serial step 1, B 2^32 by the owner wave) and of enc64 /
+enc_passes_chunk.  FIX holds the constants of the fix-ups, so a test can zero
+one and see which sums change.
 """
 from __future__ import annotations
 
@@ -204,7 +205,7 @@ def schedule_of(t):
 
 
 def serial(x, nbt, na, handoff=False):
-    """bsgs64::body step 1 (TR = 0) and the owner waves' shift32 of step 3:
+    """bsgs64::body step 1 (serial) and the owner waves' shift32 of step 3:
     babies B_b = x^b (b = 1..nbt), giants A_a = x^(nbt a) (a = 1..na - 1), the
     hand-off x^(nbt na).  Returns (babies, shifted babies, giants incl. A_1,
     hand-off or None, events)."""

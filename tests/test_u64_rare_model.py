@@ -153,19 +153,25 @@ def test_dispatch_is_the_sources():
     p64 = hip[hip.index("static int enc_passes_chunk(qk_ctx *ctx, const uint64_t *ids"):hip.index("// The x^base cache holds")]
     assert "const uint32_t npass = (T - 80 + 79) / 80;" in p64
     assert "const uint32_t Tp = std::min<uint32_t>(80, T - base);" in p64
-    assert "if (xc) launch(k_encode_u64_bsgs_x80<1>, nb, s, ids, (uint64_t)n, head, 80u, partials, xc);" in p64
+    assert "if (xc) launch(k_encode_u64_bsgs_x80, nb, s, ids, (uint64_t)n, head, 80u, partials, xc);" in p64
     assert "const int xcm = !xc ? 0 : 1 | (pass < npass ? 2 : 0);" in p64
     assert "rc = off(std::integral_constant<int, 10>{}, std::integral_constant<int, 3>{});" in p64
     na = re.search(r"rc = with_int\(\(Tp \+ 7\) / 8, ints<([\d, ]+)>\{\}, QK_E_THRESHOLD,", p64).group(1)
     assert [int(v) for v in na.split(",")] == list(range(1, 11))
-    # every product kernel: the serial step 1 (TR = 0), B 2^32 recomputed by the owner wave (BSH)
-    assert "int XC = 0, int NBT = NB, int PRIO = 0, int TR = 0>" in hdr
-    bodies = re.findall(r"bsgs64::body<([^>]*)>", hip)
-    assert len(bodies) == 4
-    for args in bodies:
-        a = [v.strip() for v in args.split(",")]
-        assert len(a) == 11 and a[6] == "true", args      # no TR argument; BSH
-    assert [a.split(",")[9].strip() for a in bodies] == ["bsgs64::NB", "4", "bsgs64::NB", "bsgs64::NB"]
+    # every product kernel: the serial step 1 is the only step 1, B 2^32 is recomputed by the owner wave
+    assert "pow_tree" not in hdr and "mulv2" not in hdr and hdr.count("// ---- step 1") == 1
+    step1 = hdr[hdr.index("// ---- step 1"):hdr.index("__syncthreads();", hdr.index("// ---- step 1"))]
+    assert "for (int b = 0; b < NBT; ++b) {\n            if (b) mulv(V, x0, x1);\n" in step1
+    assert "mulv(V, g0, g1);\n            sm.ga[G8 ? a - 1 : a][tid]" in step1 and "shift32" not in step1
+    assert hdr.count("struct Smem") == 1                               # one layout: babies and giants as (lo, hi)
+    smem = hdr[hdr.index("struct Smem {"):hdr.index("};", hdr.index("struct Smem {"))]
+    assert re.findall(r"^\s+(\w+) (\w+)\[", smem, re.M) == [("uint2", "bb"), ("uint2", "ga")]
+    step3 = hdr[hdr.index("// ---- step 3"):hdr.index("// ---- reduction")]
+    assert "const uint2 B = sm.bb[cb + c][j];\n                const uint64_t sh = shift32(" in step3
+    assert "template <int NA_, int NBT_, int SG_, int XC_ = 0, bool OFF_ = false>\nstruct Cfg {" in hdr
+    bodies = re.findall(r"bsgs64::body<bsgs64::Cfg<([^>]*)>>", hip)
+    assert len(bodies) == hip.count("bsgs64::body<") == 4
+    assert [a.split(",")[1].strip() for a in bodies] == ["8", "4", "8", "8"]      # babies per id (NBT)
     assert "constexpr int NB = 8;" in hdr
 
     # the map, at the thresholds the GPU tests run: both ends of every dispatch row

@@ -21,8 +21,10 @@ import os
 import sys
 
 PEAK_GBPS = 8000.0
-ROWS = [("void qk::k_encode_u32_bsgs<8, 4, 8, 1>", 4.0e9, "configs[1] (the bench line): encode 1e9 u32 ids, t=32"),
-        ("void qk::k_encode_u64_bsgs<10, 14, 1>", 8.0e9, "configs[2]: encode 1e9 u64 ids, t=80"),
+# name prefixes: the encode kernels are k_encode_u32_bsgs<8, 4, 8> and
+# k_encode_u64_bsgs<10, 14> (traces recorded up to round 6 carry a trailing ", 1")
+ROWS = [("void qk::k_encode_u32_bsgs<8, 4, 8", 4.0e9, "configs[1] (the bench line): encode 1e9 u32 ids, t=32"),
+        ("void qk::k_encode_u64_bsgs<10, 14", 8.0e9, "configs[2]: encode 1e9 u64 ids, t=80"),
         ("void qk::k_root_scan_k<unsigned int, 1>", 4.0e8, "configs[4]: root-set scan of 1e8 u32 candidates, d=32"),
         ("void qk::k_root_scan_k<unsigned long, 1>", 8.0e8, "configs[4] u64 twin: root-set scan of 1e8 u64 candidates"),
         ("qk::k_flow_extract", 6.7e9, "f1: per-flow extract of 1e8 x 67-byte records, 1e6 flows (record bytes)"),

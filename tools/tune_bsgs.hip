@@ -5,10 +5,11 @@
 // (constant wall clock) around its body, so the harness also reports the
 // shader clock the body actually ran at.
 //
-// Variants: bsgs::body<8, 4, SG> (sidekick_amd/csrc/bsgs.h) for several SG =
-// number of 4-wide accumulator groups whose wraps are counted on the scalar
-// unit (groups 0-1: the a = 0 add row, 2-7: MAC rows), plus the previous
-// product kernel (compiler-generated a = 0 row, canon of each id).
+// Variants: bsgs::body<bsgs::Cfg<8, 4, SG, PRIO>> (sidekick_amd/csrc/bsgs.h)
+// for several SG = number of 4-wide MAC groups whose wraps are counted on the
+// scalar unit, with and without the wave priority, at 4 or 5 waves per SIMD;
+// the round-1 product kernel (compiler-generated a = 0 row, canon of each id)
+// is kept below for reference.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -165,32 +166,15 @@ __global__ __launch_bounds__(BLOCK, 3) void k_legacy(const uint32_t *ids, uint64
     clk_end(clk, c0, r0);
 }
 
-template <int SG, int ROW0, int FOLD, bool PAIR = false, int MINW = 3>
-__global__ __launch_bounds__(BLOCK, MINW) void k_sg(const uint32_t *ids, uint64_t n, uint64_t *partials,
-                                                    uint64_t *clk) {
+// bsgs::Cfg<8, 4, SG, PRIO> at MINW waves per SIMD: what the header can express.
+// SG = scalar-counted 4-wide MAC groups (of 6), PRIO = s_setprio over each
+// id's accumulation (row 0 at 1, the MAC rows at 2).
+template <int SG, bool PRIO, int MINW>
+__global__ __launch_bounds__(BLOCK, MINW) void k_var(const uint32_t *ids, uint64_t n, uint64_t *partials,
+                                                     uint64_t *clk) {
     uint64_t c0, r0;
     clk_begin(c0, r0);
-    bsgs::body<bsgs::Cfg<8, 4, SG, ROW0, FOLD, PAIR>>(ids, n, 0, T, partials);
-    clk_end(clk, c0, r0);
-}
-
-// s_setprio around the MAC phase (bsgs.h Cfg PRIO)
-template <int PRIO, int SG = 8, int MINW = 5, bool TREE = false, bool PAIR = false>
-__global__ __launch_bounds__(BLOCK, MINW) void k_prio(const uint32_t *ids, uint64_t n, uint64_t *partials,
-                                                      uint64_t *clk) {
-    uint64_t c0, r0;
-    clk_begin(c0, r0);
-    bsgs::body<bsgs::Cfg<8, 4, SG, 1, 1, PAIR, false, 0, TREE, PRIO>>(ids, n, 0, T, partials);
-    clk_end(clk, c0, r0);
-}
-
-// product-tree babies (bsgs.h Cfg TREE): same modmuls, dependency depth 3
-template <int MINW>
-__global__ __launch_bounds__(BLOCK, MINW) void k_tree(const uint32_t *ids, uint64_t n, uint64_t *partials,
-                                                      uint64_t *clk) {
-    uint64_t c0, r0;
-    clk_begin(c0, r0);
-    bsgs::body<bsgs::Cfg<8, 4, 8, 1, 1, false, false, 0, true>>(ids, n, 0, T, partials);
+    bsgs::body<bsgs::Cfg<8, 4, SG, PRIO>>(ids, n, 0, T, partials);
     clk_end(clk, c0, r0);
 }
 
@@ -225,11 +209,12 @@ int main(int argc, char **argv) {
     hipLaunchKernelGGL(k_fill, dim3(4096), dim3(256), 0, 0, ids, n, 0x5EED0002ull);
     CHK(hipDeviceSynchronize());
 
-    // SG counts row-0 groups (0-1) only when ROW0 == 0; with ROW0 == 1 the
-    // scalar groups start at the first MAC group (g = 2)
-    // round-1 measurements: legacy 3.13 ms; row 0 as mads +
-    // min-tracked folds + all MAC wraps scalar (r1f1_sg8) 2.73 ms at 4 waves,
-    // 2.67 ms at 5 waves; burst-free interleaved scalar counting 3.12 ms;
+    // The variants this harness measured and the header no longer carries (in
+    // git at a33fab6; DESIGN.md §3.2 lists each with its profile file):
+    // round 1: legacy 3.13 ms; row 0 as mads + min-tracked
+    // folds + all MAC wraps scalar 2.73 ms at 4 waves, 2.67 ms at 5 waves (row 0
+    // as 32-bit adds with counted wraps and SGPR-carry folds: the forms it
+    // replaced); burst-free interleaved scalar counting 3.12 ms;
     // compiler-scheduled popcounts spill SGPRs; the whole accumulate as one
     // asm statement (no asm-boundary nops) 2.71 vs 2.71 ms.  Ablations (wrong sums): no
     // scalar counting 2.58 ms, no MACs 1.69 ms.
@@ -239,17 +224,16 @@ int main(int argc, char **argv) {
     // waves/SIMD 2.73 vs 2.63-2.66, 7 / 6 scalar-counted groups 3.42 / 4.05,
     // product-tree babies 2.57; again (tune_bsgs_prio_tree.json) tree 2.559 /
     // 2.569 vs product 2.559 / 2.587: even, not adopted; two ids interleaved
-    // (PAIR) under priority 2.72 (w4) vs 2.64-2.71 (tune_bsgs_prio_pair.json).
+    // under priority 2.72 (w4) vs 2.64-2.71 (tune_bsgs_prio_pair.json).
     // The priority window without row 0 2.67 / 2.67, row 0 at 1 and the MAC
     // rows at 2 2.652 / 2.654 vs 2.720 / 2.733 (tune_bsgs_prio_levels.json).
     // More schemes (tune_bsgs_prio_levels2.json): rows rising 2 -> 3 2.68,
-    // row 0 above the rows 2.70, 4 waves 2.75.  This set: row 0 after the MAC
-    // rows
-    std::vector<Var> vars = {{"prio_row0_1_macrows_2_w5 (product)", k_prio<4>},
-                             {"prio_macrows_2_then_row0_1_w5", k_prio<7>},
-                             {"prio_mac_w5 (one level)", k_prio<1>},
-                             {"prio_row0_1_macrows_2_w5_again", k_prio<4>},
-                             {"prio_macrows_2_then_row0_1_w5_again", k_prio<7>}};
+    // row 0 above the rows 2.70, 4 waves 2.75; row 0 after the MAC rows
+    // (tune_bsgs_prio_row0_order.json).
+    // What remains to vary: SG, the priority on or off, waves per SIMD.
+    std::vector<Var> vars = {{"sg8_prio_w5 (product)", k_var<8, true, 5>}, {"sg8_noprio_w5", k_var<8, false, 5>},
+                             {"sg7_prio_w5", k_var<7, true, 5>},           {"sg6_prio_w5", k_var<6, true, 5>},
+                             {"sg8_prio_w4", k_var<8, true, 4>},           {"sg8_prio_w5_again", k_var<8, true, 5>}};
     uint32_t ref[T], got[T];
     std::vector<std::vector<float>> times(vars.size());
     std::vector<double> mhz(vars.size(), 0.0);
