@@ -281,6 +281,50 @@ int qk_u32_encode_flows_device(qk_ctx *ctx, const uint8_t *d_bufs, size_t n, siz
  * segment) -> nseg sketches (qk_u32_size(threshold) bytes each). */
 int qk_u32_encode_segments_device(qk_ctx *ctx, const uint32_t *d_ids, const uint64_t *offsets, size_t nseg,
                                   uint32_t threshold, uint8_t *sketches, void *stream);
+/* Per-flow quACK snapshots: the quACK the proxy sends after every packet that
+ * brings its flow's count to a multiple of frequency_pkts
+ * (sidekick_multi.rs:271-283: `let quack = sc.insert(addr_key, id); if
+ * quack.count() % frequency_pkts == 0 { bincode::serialize(&quack) .. }`), for
+ * a batch grouped by flow: every crossing inside the batch, not only the flow's
+ * end-of-batch state.  A segmented prefix encode.
+ * d_base: nseg qk_u32 records of qk_u32_size(threshold) bytes in device memory,
+ * row g the quACK of flow g before the batch (a flow the table has not seen: a
+ * qk_u32_init row).  d_ids and host offsets[nseg + 1]: the batch's ids grouped
+ * by flow in arrival order, as in qk_u32_encode_segments_device; a segment
+ * holds fewer than 2^32 ids.  d_arrival (may be NULL): a parallel u32 array,
+ * the index each packet had in the ungrouped batch, only carried through to
+ * d_snap_arrival_out so that a caller can put the snapshots of all flows into
+ * the order the reference would have sent them; both NULL or both set.
+ * For segment g with base count c0 and local positions j = 0 .. n_g - 1: after
+ * packet j the count is c = (c0 + j + 1) mod 2^32, and packet j triggers a
+ * snapshot iff c % frequency_pkts == 0, on the wrapped u32 as the reference's
+ * u32 does, so a count that wraps to 0 triggers (on purpose not the 64-bit rule
+ * of qk_u32_flows_merge_device's due_out).  The snapshot record: threshold,
+ * count = c, has_last = 1, last_value = ids[offsets[g] + j] (unreduced),
+ * power_sums[k-1] = base.S_k + sum over i <= j of (id_i mod p)^k, canonical.
+ * Snapshots come out ordered by flow, then by position: snap_offsets[nseg + 1]
+ * (host) is their CSR index by flow, d_snap_seg_out[r] = g, d_snap_pos_out[r] =
+ * offsets[g] + j, d_snap_arrival_out[r] = d_arrival[offsets[g] + j].
+ * d_final_out (may be NULL): nseg records, the end-of-batch state of every
+ * flow, qk_u32_merge(base_g, the encode of segment g); base_g unchanged for an
+ * empty segment: the caller's table update needs no second pass over the ids.
+ * NULL ctx -> QK_E_INVAL before any other check; threshold 0 or > 1024 ->
+ * QK_E_THRESHOLD; frequency_pkts == 0, decreasing offsets, nseg >= 2^32, a
+ * segment of 2^32 ids or more, a host pointer where a device one is required or
+ * the reverse, one arrival pointer without the other, an output range
+ * overlapping an input or another output (d_final_out against d_base included)
+ * -> QK_E_INVAL; a base record whose threshold field differs (found on the
+ * device) -> QK_E_MISMATCH, the outputs unspecified; cap < the snapshots ->
+ * QK_E_CAPACITY with *n_snap and snap_offsets fully written and no device
+ * output written (a repeat with a larger cap gives the same result); nseg == 0
+ * -> QK_OK with snap_offsets[0] = 0.  Synchronous on `stream`; every array is
+ * 4-byte aligned. */
+int qk_u32_snapshot_segments_device(qk_ctx *ctx, const uint8_t *d_base, const uint32_t *d_ids,
+                                    const uint32_t *d_arrival, const uint64_t *offsets, size_t nseg,
+                                    uint32_t threshold, uint32_t frequency_pkts, uint8_t *d_snap_out,
+                                    uint32_t *d_snap_seg_out, uint64_t *d_snap_pos_out,
+                                    uint32_t *d_snap_arrival_out, size_t cap, uint64_t *snap_offsets,
+                                    size_t *n_snap, uint8_t *d_final_out, void *stream);
 
 /* ------------------------------------------------------------------------
  * Decode-missing root test.  Replaces media_client.rs:306-313:
@@ -487,8 +531,8 @@ int qk_u32_log_update_segments_device(qk_ctx *ctx, const uint32_t *d_log, const 
  *   (before + b.count) / frequency_pkts > before / frequency_pkts, evaluated in 64 bits,
  *   where before = the a source's count, or 0 without one.
  *   This flags the flows for which start_sidekick_multi_frequency_pkts
- *   (sidekick_multi.rs:274) would have emitted during the batch; the quACK a
- *   caller then sends is the end-of-batch one, not a mid-batch snapshot.
+ *   (sidekick_multi.rs:274) would have emitted during the batch; the quACKs
+ *   themselves, one per crossing, come from qk_u32_snapshot_segments_device.
  *   0 otherwise, and all 0 when frequency_pkts == 0.
  * *n_out = flows in the union.
  * cap < *n_out -> QK_E_CAPACITY with *n_out set and no output array written. */

@@ -196,6 +196,13 @@ extern "C" {
                                       stats: *mut qk_pkt_stats, stream: *mut c_void) -> c_int;
     pub fn qk_u32_encode_segments_device(ctx: *mut qk_ctx, d_ids: *const u32, offsets: *const u64, nseg: usize,
                                          threshold: u32, sketches: *mut u8, stream: *mut c_void) -> c_int;
+    // the quACK after every packet that brings its flow's count to a multiple of frequency_pkts
+    pub fn qk_u32_snapshot_segments_device(ctx: *mut qk_ctx, d_base: *const u8, d_ids: *const u32,
+                                           d_arrival: *const u32, offsets: *const u64, nseg: usize,
+                                           threshold: u32, frequency_pkts: u32, d_snap_out: *mut u8,
+                                           d_snap_seg_out: *mut u32, d_snap_pos_out: *mut u64,
+                                           d_snap_arrival_out: *mut u32, cap: usize, snap_offsets: *mut u64,
+                                           n_snap: *mut usize, d_final_out: *mut u8, stream: *mut c_void) -> c_int;
 
     // root test / decode
     pub fn qk_u32_root_test_device(ctx: *mut qk_ctx, coeffs: *const u32, d: u32, d_log: *const u32, n: usize,

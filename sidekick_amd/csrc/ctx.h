@@ -186,6 +186,7 @@ int warm_segments(hipStream_t s);
 int warm_segdecode(hipStream_t s);
 int warm_sender(hipStream_t s);
 int warm_senderlog(hipStream_t s);
+int warm_snapshots(hipStream_t s);
 int warm_flowtable(hipStream_t s);
 int warm_wire(hipStream_t s);
 int warm_comm(hipStream_t s);

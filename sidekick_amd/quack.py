@@ -28,6 +28,10 @@ plus the batch entry points of the MI355X engine:
                              packets, one pass over the device-resident log.
     DeviceSenderLog          QuackReceiver for many flows: log, seqnos and my
                              quACKs stay in HBM between send and on_quacks.
+    snapshot_segments(..)    the quACK after every packet that brings its flow's
+                             count to a multiple of frequency_pkts, for a batch.
+    DeviceFlowSnapshots      the proxy's table by flow index: a batch in, the
+                             datagrams of sidekick_multi.rs:271-283 out, in order.
     flows_merge / flows_diff / flows_lookup, DeviceFlowQuacks
                              SidekickMulti's flow table as key-sorted arrays in
                              HBM: merge a batch, diff against a peer, look up.
@@ -59,6 +63,7 @@ __all__ = [
     "arithmetic", "Context", "get_context", "device_count", "FlowQuacks",
     "to_coeffs_segments", "decode_segments", "sender_step", "drain_segments", "SenderStep",
     "update_segments", "DeviceSenderLog", "SenderLogStep",
+    "snapshot_segments", "Snapshots", "DeviceFlowSnapshots",
     "flows_merge", "flows_diff", "flows_lookup", "DeviceFlowQuacks",
     "emit_wire", "ingest_wire", "wire_max",
 ]
@@ -814,6 +819,137 @@ class DeviceSenderLog:
                 self._peer[:min(nf, old.shape[0])] = old[:nf]
         _, present, status, _ = ingest_wire(wire, lens, flow, nf, self.threshold, peer=self._peer, ctx=self._ctx)
         return self.on_quacks(self._peer, present=present, now=now), status
+
+
+@dataclass
+class Snapshots:
+    """What snapshot_segments returns: the m snapshots ordered by flow, then by position."""
+    records: object      # CUDA int32 [m, 4 + t]: the quACK after each triggering packet
+    seg: object          # CUDA int32 [m]: the flow (segment) of each snapshot
+    pos: object          # CUDA int64 [m]: the position of its triggering packet in `ids`
+    arrival: object      # CUDA int32 [m]: `arrival` at that position, or None
+    offsets: np.ndarray  # host uint64 [nseg + 1]: the CSR index of the snapshots by flow
+    final: object        # CUDA int32 [nseg, 4 + t]: every flow's end-of-batch quACK, or None
+
+
+def snapshot_segments(base, ids, offsets, frequency_pkts: int, arrival=None, final=False,
+                      ctx: Context | None = None) -> Snapshots:
+    """The quACK after every packet that brings its flow's count to a multiple
+    of `frequency_pkts` (sidekick_multi.rs:271-283), for a batch grouped by flow,
+    on the device (qk_u32_snapshot_segments_device).  `base`: one quACK per flow
+    as it was before the batch (a list of PowerSumQuackU32 of one threshold, or
+    a CUDA int32 record tensor [nseg, 4 + t]); `ids`: the batch grouped by flow
+    in arrival order (a CUDA u32/int32 tensor, or a host array, uploaded) with
+    CSR `offsets`; `arrival`: an optional parallel array carried through to the
+    snapshots.  `final`: True for every flow's end-of-batch quACK as well, or a
+    record tensor [nseg, 4 + t] to write it into (not `base`)."""
+    ctx = _context(ctx, base, ids)
+    torch = need_torch()
+    r = Records.parse(base, PowerSumQuackU32)
+    device = torch.device(f"cuda:{ctx.device}")
+    d_base = r.to_device(ctx, "snapshot_segments") if r.nseg else None
+    t, W = r.t, 4 + r.t
+    ids = uint_on_device(ids, device, "ids")
+    n = ids.numel()
+    offs, nseg = csr(offsets, "base", r.nseg, n)
+    f = int(frequency_pkts)
+    if not 0 <= f < 1 << 32:
+        raise ValueError("frequency_pkts must fit a u32")
+    if arrival is not None:
+        arrival = uint_on_device(arrival, device, "arrival")
+        if arrival.numel() != n:
+            raise ValueError("arrival must be as long as ids")
+    if final is True:
+        final = torch.empty((nseg, W), dtype=torch.int32, device=device)
+    elif final is False or final is None:
+        final = None
+    elif not (is_record_tensor(final, 0) and tuple(final.shape) == (nseg, W) and final.device == device):
+        raise TypeError("final must be a contiguous CUDA int32 record tensor [nseg, 4 + t] on the device of ids")
+    lens = offs[1:] - offs[:-1]
+    # at most one snapshot per packet, and per flow one per frequency_pkts packets, one for the phase, one for the wrap
+    bound = int(np.minimum(lens, lens // np.uint64(f) + np.uint64(2)).sum()) if f and not np.any(offs[1:] < offs[:-1]) else 0
+    snoffs = np.zeros(nseg + 1, dtype=np.uint64)
+    stream = stream_of(ids)
+
+    def attempt(cap):
+        rows = max(cap, 1)   # an empty tensor has no address, and the arrival pointers go together
+        rec = torch.empty((rows, W), dtype=torch.int32, device=device)
+        seg = torch.empty((rows,), dtype=torch.int32, device=device)
+        pos = torch.empty((rows,), dtype=torch.int64, device=device)
+        arr = torch.empty((rows,), dtype=torch.int32, device=device) if arrival is not None and n else None
+        m = C.c_size_t()
+        rc = lib().qk_u32_snapshot_segments_device(
+            ctx.handle, d_base.data_ptr() if nseg else None, ids.data_ptr() if n else None,
+            arrival.data_ptr() if arr is not None else None, ptr(offs), nseg, t, f,
+            rec.data_ptr(), seg.data_ptr(), pos.data_ptr(), arr.data_ptr() if arr is not None else None, cap,
+            ptr(snoffs), C.byref(m), final.data_ptr() if final is not None and nseg else None, stream)
+        if arr is None and arrival is not None:
+            arr = seg   # no ids: no snapshot, an empty slice of it
+        return rc, m.value, (rec, seg, pos, arr, m.value)
+    rec, seg, pos, arr, m = retry_capacity(attempt, bound, "snapshot_segments")
+    return Snapshots(rec[:m], seg[:m], pos[:m], arr[:m] if arr is not None else None, snoffs, final)
+
+
+class DeviceFlowSnapshots:
+    """The proxy's flow table addressed by flow index, in HBM: the twin of
+    DeviceSenderLog on the other end.  insert() takes an ungrouped batch of
+    (flow, id) in arrival order and returns the datagrams
+    start_sidekick_multi_frequency_pkts (sidekick_multi.rs:271-283) would have
+    sent for it, in its order: one per packet that brought its flow's count to
+    a multiple of frequency_pkts.  `records` (CUDA int32 [nflows, 4 + t]) is
+    the table; two tensors take turns, since the snapshot call writes the
+    end-of-batch table beside the one it reads."""
+
+    def __init__(self, threshold: int, nflows: int, frequency_pkts: int, device: int = 0):
+        self.threshold = int(threshold)
+        self.frequency_pkts = int(frequency_pkts)
+        self._ctx = get_context(device)          # no device: QK_E_NO_DEVICE, nothing falls back
+        torch = need_torch()
+        self._device = torch.device(f"cuda:{device}")
+        self._fresh = _fresh_record(self.threshold, self._device)
+        self.records = torch.empty((0, 4 + self.threshold), dtype=torch.int32, device=self._device)
+        self._spare = None
+        self.add_flows(nflows)
+
+    @property
+    def nflows(self) -> int:
+        return self.records.shape[0]
+
+    def add_flows(self, k: int) -> None:
+        """k more flows, each with a fresh quACK."""
+        k = int(k)
+        if k < 0:
+            raise ValueError("k must not be negative")
+        self.records = need_torch().cat([self.records, self._fresh.unsqueeze(0).expand(k, -1)]).contiguous()
+        self._spare = None
+
+    def insert(self, flow, ids, stride: int | None = None):
+        """sc.insert(flow[i], ids[i]) for every i, in this order.  Returns
+        (flow_of_image, wire, lens, records): CUDA tensors, datagram r the
+        bincode image wire[r, :lens[r]] of records[r], the quACK of flow
+        flow_of_image[r] after its triggering packet, in the order the
+        reference would have sent them."""
+        torch = need_torch()
+        n = uint_len(flow, "flow")
+        if uint_len(ids, "ids") != n:
+            raise ValueError("flow and ids must be equally long")
+        dev, nf, t = self._device, self.nflows, self.threshold
+        empty = torch.empty((0,), dtype=torch.int32, device=dev)
+        # grouped stably by flow, the arrival index riding along
+        grouped, goffs, garr = update_segments(empty, np.zeros(nf + 1, dtype=np.uint64), None, flow, ids, aux=empty,
+                                               new_aux=torch.arange(n, dtype=torch.int32, device=dev), ctx=self._ctx)
+        if self._spare is None:
+            self._spare = torch.empty_like(self.records)
+        s = snapshot_segments(self.records, grouped, goffs, self.frequency_pkts, arrival=garr, final=self._spare,
+                              ctx=self._ctx)
+        self.records, self._spare = self._spare, self.records
+        stride = wire_max(t) if stride is None else int(stride)
+        if s.records.shape[0] == 0:
+            return (s.seg, torch.empty((0, stride), dtype=torch.uint8, device=dev), s.seg.clone(), s.records)
+        order = torch.argsort(s.arrival.to(torch.int64) & 0xFFFFFFFF)
+        recs = s.records[order].contiguous()
+        _, _, wire, lens = emit_wire(None, recs, stride=stride, ctx=self._ctx)
+        return s.seg[order], wire, lens, recs
 
 
 def encode_flows(bufs, threshold: int, stride: int = 67, meta=None, my_addr=None, ctx: Context | None = None,
