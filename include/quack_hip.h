@@ -608,12 +608,15 @@ int qk_u32_flows_emit_device(qk_ctx *ctx, const qk_flow_key *d_keys, const uint8
  * min(d_len[i], stride) of a slot is read, whatever the image claims.
  * Last wins — a rule of the batch (the reference handles one datagram per loop
  * turn; quACKs are cumulative, so a sender that received several for a flow
- * since its last step needs only the newest): among the accepted datagrams of
+ * since its last step needs only the newest as long as the losses of all of
+ * them together stay <= threshold; beyond that the newest alone ends in
+ * QK_SND_RESET_EXCEEDS where stepping each would have recovered every packet:
+ * qk_u32_wire_ingest_queue_device keeps them all): among the accepted datagrams of
  * flow g the one with the largest i goes to row g of d_peer (nseg records of
  * qk_u32_size(threshold) bytes; the threshold field set to `threshold`) with
  * d_present[g] = 1, and the flow's earlier accepted datagrams get status
- * QK_WIRE_SUPERSEDED (a caller that wants every quACK stepped runs those in an
- * earlier call).  A flow without an accepted datagram gets d_present[g] = 0
+ * QK_WIRE_SUPERSEDED (a caller that wants every quACK stepped takes
+ * qk_u32_wire_ingest_queue_device and qk_u32_sender_steps_segments_device).  A flow without an accepted datagram gets d_present[g] = 0
  * and keeps its d_peer row.  *n_accepted = the winners.
  * A d_flow[i] >= nseg (found on the device) -> QK_E_INVAL before d_peer or
  * d_present is written.  n == 0 -> QK_OK with d_present all zero; nseg == 0
@@ -622,6 +625,72 @@ int qk_u32_wire_ingest_device(qk_ctx *ctx, const uint8_t *d_wire, size_t stride,
                               const uint32_t *d_flow, size_t n, uint32_t threshold, size_t nseg,
                               uint8_t *d_peer, uint8_t *d_present, int32_t *status, size_t *n_accepted,
                               void *stream);
+
+/* ------------------------------------------------------------------------
+ * Every queued quACK of a flow stepped in one call: the loop of
+ * media_client.rs:223-323 over ALL datagrams a batch brought for a flow, one
+ * per loop turn as the reference takes them, where qk_u32_wire_ingest_device
+ * and qk_u32_sender_step_segments_device take the newest only.
+ * ---------------------------------------------------------------------- */
+/* qk_u32_wire_ingest_device's inputs, validation (one rule set) and status[i]
+ * values, but nothing is superseded: every accepted image is parsed into a
+ * qk_u32 record of d_queue (cap records of qk_u32_size(threshold) bytes, the
+ * threshold field set to `threshold`), the records grouped by flow and, within
+ * a flow, in arrival order (ascending i; the placement is stable).
+ * q_offsets[nseg + 1] (host, q_offsets[0] = 0) is their CSR index by flow,
+ * *n_accepted = q_offsets[nseg].  cap < *n_accepted -> QK_E_CAPACITY with
+ * q_offsets, status and *n_accepted written and d_queue untouched.  A
+ * d_flow[i] >= nseg (found on the device) -> QK_E_INVAL before any output
+ * array is written; nseg == 0 with n > 0, stride == 0, n >= 2^32, nseg >=
+ * 2^32 - 1 (the sort key of a rejected datagram is nseg), d_queue overlapping
+ * an input, a host pointer where a device one is required or the reverse ->
+ * QK_E_INVAL.  n == 0 -> QK_OK, q_offsets all
+ * zero.  Synchronous on `stream`. */
+int qk_u32_wire_ingest_queue_device(qk_ctx *ctx, const uint8_t *d_wire, size_t stride, const uint32_t *d_len,
+                                    const uint32_t *d_flow, size_t n, uint32_t threshold, size_t nseg,
+                                    uint8_t *d_queue, size_t cap, uint64_t *q_offsets, int32_t *status,
+                                    size_t *n_accepted, void *stream);
+
+/* action of a queued quACK behind its flow's first reset: not stepped */
+#define QK_SND_UNSTEPPED 16u
+/* Per flow g, with step() = what qk_u32_sender_step_segments_device does for
+ * one flow and one quACK:
+ *   m = mine[g]; b = 0
+ *   for j in 0 .. k_g - 1, q = q_offsets[g] + j:       the flow's quACKs in queue order
+ *     (m, action, d, missing) = step(m, queue[q], log_g[b ..], threshold)
+ *     q_action[q] = action; q_drain[q] = d; hits of q = missing + b (+ offsets[g])
+ *     a reset bit in action: stop; the later quACKs of the flow keep
+ *       QK_SND_UNSTEPPED, q_drain 0 and no hits
+ *     b += d
+ *   mine_out[g] = m; drain[g] = b; stepped[g] = the quACKs consumed (the
+ *   resetting one included).
+ * The log is not moved: b is an offset, the drain stays with
+ * qk_u32_log_update_segments_device.  The intervals of successive quACKs are
+ * disjoint and ascending, so hits (global positions into d_log) ascend over
+ * the whole call; hit_offsets[nq + 1] is their CSR index by quACK, nq =
+ * q_offsets[nseg].  A flow stops at its first reset because the debounce is
+ * the caller's and depends on time: when the reset fires, the flow is cleared
+ * and its later quACKs change nothing; when it is held back, the caller goes
+ * on from mine_out with a second call on the unstepped tail.  A flow with k_g
+ * == 0 is idle; with k_g <= 1 everywhere the outputs equal
+ * qk_u32_sender_step_segments_device's.
+ * d_mine, d_mine_out: nseg records; d_queue: nq records, q_offsets[nseg + 1]
+ * (host, q_offsets[0] = 0) as qk_u32_wire_ingest_queue_device writes them;
+ * d_log / offsets as in the single step.  q_action, q_drain (nq entries),
+ * stepped, drain (nseg), hits, hit_offsets and n_hits are host memory.
+ * Synchronous on `stream`.
+ * NULL ctx -> QK_E_INVAL before any other check; threshold 0 or > 1024 ->
+ * QK_E_THRESHOLD; a host pointer where a device one is required (or the
+ * reverse), decreasing offsets or q_offsets, q_offsets[0] != 0, or d_mine_out
+ * overlapping an input -> QK_E_INVAL; a record of mine or of the queue whose
+ * threshold field differs -> QK_E_MISMATCH; cap < total -> QK_E_CAPACITY with
+ * *n_hits and every output but hits written (a repeat with a larger cap gives
+ * the same outputs); nseg == 0 -> QK_OK with hit_offsets[0] = 0. */
+int qk_u32_sender_steps_segments_device(qk_ctx *ctx, const uint8_t *d_mine, const uint8_t *d_queue,
+                                        const uint64_t *q_offsets, const uint32_t *d_log, const uint64_t *offsets,
+                                        size_t nseg, uint32_t threshold, uint8_t *d_mine_out, uint8_t *q_action,
+                                        uint64_t *q_drain, uint32_t *stepped, uint64_t *drain, uint64_t *hits,
+                                        size_t cap, uint64_t *hit_offsets, size_t *n_hits, void *stream);
 
 /* ------------------------------------------------------------------------
  * Multi-GPU: the id stream cut into contiguous shards, one

@@ -29,6 +29,8 @@ pub const QK_SND_ADVANCED: u8 = 1;
 pub const QK_SND_RESET_REORDERED: u8 = 2;
 pub const QK_SND_RESET_RETX: u8 = 4;
 pub const QK_SND_RESET_EXCEEDS: u8 = 8;
+/// qk_u32_sender_steps_segments_device: a queued quACK behind its flow's first reset
+pub const QK_SND_UNSTEPPED: u8 = 16;
 
 pub const QK_OK: c_int = 0;
 pub const QK_E_INVAL: c_int = -1;
@@ -277,6 +279,17 @@ extern "C" {
                                      d_flow: *const u32, n: usize, threshold: u32, nseg: usize, d_peer: *mut u8,
                                      d_present: *mut u8, status: *mut int32_t, n_accepted: *mut usize,
                                      stream: *mut c_void) -> c_int;
+    // every queued quACK of a flow: the queue by flow, then all of it stepped in one call
+    pub fn qk_u32_wire_ingest_queue_device(ctx: *mut qk_ctx, d_wire: *const u8, stride: usize, d_len: *const u32,
+                                           d_flow: *const u32, n: usize, threshold: u32, nseg: usize,
+                                           d_queue: *mut u8, cap: usize, q_offsets: *mut u64, status: *mut int32_t,
+                                           n_accepted: *mut usize, stream: *mut c_void) -> c_int;
+    pub fn qk_u32_sender_steps_segments_device(ctx: *mut qk_ctx, d_mine: *const u8, d_queue: *const u8,
+                                               q_offsets: *const u64, d_log: *const u32, offsets: *const u64,
+                                               nseg: usize, threshold: u32, d_mine_out: *mut u8, q_action: *mut u8,
+                                               q_drain: *mut u64, stepped: *mut u32, drain: *mut u64,
+                                               hits: *mut u64, cap: usize, hit_offsets: *mut u64,
+                                               n_hits: *mut usize, stream: *mut c_void) -> c_int;
 
     // multi-GPU over RCCL
     pub fn qk_comm_unique_id(id: *mut u8) -> c_int;

@@ -36,6 +36,7 @@ SND_ADVANCED = 1
 SND_RESET_REORDERED = 2
 SND_RESET_RETX = 4
 SND_RESET_EXCEEDS = 8
+SND_UNSTEPPED = 16         # qk_u32_sender_steps_segments_device: a queued quACK behind its flow's first reset
 QK_WIRE_SUPERSEDED = 1   # qk_u32_wire_ingest_device: a well-formed image that a later one of the same flow replaced
 FLOW_JOIN_TILE = 2048   # QK_FLOW_JOIN_TILE: keys of a and b together per work item of the flow-table join
 
@@ -128,6 +129,10 @@ SIGNATURES = {
     "qk_u32_flows_emit_device": (C.c_int, [vp, vp, vp, sz, C.c_uint32, vp, sz, vp, vp, vp, vp, sz, szp, vp]),
     "qk_u32_wire_ingest_device": (C.c_int, [vp, vp, sz, vp, vp, sz, C.c_uint32, sz, vp, vp, C.POINTER(C.c_int32), szp,
                                             vp]),
+    "qk_u32_wire_ingest_queue_device": (C.c_int, [vp, vp, sz, vp, vp, sz, C.c_uint32, sz, vp, sz, u64p,
+                                                  C.POINTER(C.c_int32), szp, vp]),
+    "qk_u32_sender_steps_segments_device": (C.c_int, [vp, vp, vp, u64p, vp, u64p, sz, C.c_uint32, vp, u8p, u64p, u32p,
+                                                      u64p, u64p, sz, u64p, szp, vp]),
     "qk_comm_unique_id": (C.c_int, [u8p]),
     "qk_comm_create": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(vp)]),
     "qk_comm_init_rank": (C.c_int, [u8p, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),

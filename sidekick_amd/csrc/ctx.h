@@ -185,6 +185,7 @@ int warm_flows(hipStream_t s);
 int warm_segments(hipStream_t s);
 int warm_segdecode(hipStream_t s);
 int warm_sender(hipStream_t s);
+int warm_sendersteps(hipStream_t s);
 int warm_senderlog(hipStream_t s);
 int warm_snapshots(hipStream_t s);
 int warm_flowtable(hipStream_t s);

@@ -89,6 +89,12 @@ int sd_upload(qk_ctx *ctx, SdPlan &p, const uint64_t *offsets, size_t nseg, hipS
 // sd_upload (diffs: nseg records, host or device)
 int sd_enqueue(qk_ctx *ctx, SdPlan &p, const uint8_t *diffs, bool host_rec, const uint32_t *d_log, size_t nseg,
                uint32_t T, int stop_at_last, hipStream_t s);
+// the two ends of sd_enqueue for a caller with a root test of its own
+// (sendersteps.hip): Newton over nseg device or host records into b.coef /
+// b.deg / b.status; the scan of the item counts and the hit write over the
+// plan's mask
+int sd_newton(qk_ctx *ctx, const uint8_t *diffs, bool host_rec, size_t nseg, uint32_t T, SdSeg &b, hipStream_t s);
+int sd_compact(SdPlan &p, hipStream_t s);
 // after the caller has waited for s (status and segcnt copied back by it):
 // hit_offsets, *n_hits and the hits themselves
 int sd_collect(const SdPlan &p, const int32_t *status, const uint32_t *segcnt, uint64_t total, size_t nseg,

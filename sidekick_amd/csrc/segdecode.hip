@@ -281,7 +281,7 @@ static void sd_carve(Carve &cv, SdSeg &b, size_t nseg, uint32_t T, bool host_rec
 
 // records onto the device (host records: threshold checked here) and the
 // Newton kernel enqueued
-static int sd_newton(qk_ctx *ctx, const uint8_t *diffs, bool host_rec, size_t nseg, uint32_t T, SdSeg &b,
+int sd_newton(qk_ctx *ctx, const uint8_t *diffs, bool host_rec, size_t nseg, uint32_t T, SdSeg &b,
                      hipStream_t s) {
     const size_t rec = qk_u32_size(T);
     if (host_rec) {
@@ -374,7 +374,13 @@ int sd_enqueue(qk_ctx *ctx, SdPlan &p, const uint8_t *diffs, bool host_rec, cons
     prof_end(ctx, s, e0);
     hipLaunchKernelGGL(k_seg_hit_count, dim3((uint32_t)ni), dim3(SD_BLOCK), lds_cnt, s, p.d_items, b.offs, maxseg,
                        b.stop, p.d_mask, p.d_icnt, b.segcnt);
-    hipLaunchKernelGGL(k_seg_scan, dim3(1), dim3(SD_SCAN), 0, s, p.d_icnt, (uint32_t)ni, p.d_base, b.total);
+    return sd_compact(p, s);
+}
+
+int sd_compact(SdPlan &p, hipStream_t s) {
+    const size_t ni = p.items.size();
+    if (!ni) return QK_OK;
+    hipLaunchKernelGGL(k_seg_scan, dim3(1), dim3(SD_SCAN), 0, s, p.d_icnt, (uint32_t)ni, p.d_base, p.b.total);
     hipLaunchKernelGGL(k_seg_hit_write, dim3((uint32_t)ni), dim3(64), 0, s, p.d_items, p.d_mask, p.d_base, p.d_hit,
                        p.hcap);
     return hipGetLastError() == hipSuccess ? QK_OK : QK_E_HIP;

@@ -23,6 +23,8 @@ plus the batch entry points of the MI355X engine:
                              one device pass (the per-flow quACKs of SidekickMulti).
     sender_step(..)          the sender loop of media_client.rs:233-322 for many
                              flows: prefix insert, reset test, decode, removes.
+    sender_steps(..)         the same loop over every queued quACK of a flow, one
+                             after the other, in one call (ingest_wire_queue).
     drain_segments(..)       seqno_ids.drain(..idx+1) of every flow's log.
     update_segments(..)      the same drain plus seqno_ids.push of a batch of sent
                              packets, one pass over the device-resident log.
@@ -55,17 +57,17 @@ from dataclasses import dataclass
 
 from ._args import (Records, _device_array, _host_array, csr, csr_drain, dev_index, is_record_tensor,
                     need_torch, packet_batch, ptr, retry_capacity, split_hits, stream_of, uint_len, uint_on_device)
-from ._lib import (P32, P64, QK_E_CAPACITY, QK_E_INVAL, QK_E_MISMATCH, SND_ADVANCED, SND_RESET_EXCEEDS, SND_RESET_REORDERED,
-                   SND_RESET_RETX, QuackError, check, lib)
+from ._lib import (P32, P64, QK_E_CAPACITY, QK_E_INVAL, QK_E_MISMATCH, SND_ADVANCED, SND_IDLE, SND_RESET_EXCEEDS,
+                   SND_RESET_REORDERED, SND_RESET_RETX, QuackError, check, lib)
 
 __all__ = [
     "PowerSumQuackU32", "PowerSumQuackU64", "ModularInteger", "CoefficientVector",
     "arithmetic", "Context", "get_context", "device_count", "FlowQuacks",
     "to_coeffs_segments", "decode_segments", "sender_step", "drain_segments", "SenderStep",
-    "update_segments", "DeviceSenderLog", "SenderLogStep",
+    "update_segments", "DeviceSenderLog", "SenderLogStep", "sender_steps", "SenderSteps",
     "snapshot_segments", "Snapshots", "DeviceFlowSnapshots",
     "flows_merge", "flows_diff", "flows_lookup", "DeviceFlowQuacks",
-    "emit_wire", "ingest_wire", "wire_max",
+    "emit_wire", "ingest_wire", "ingest_wire_queue", "wire_max",
 ]
 
 
@@ -611,6 +613,74 @@ def sender_step(mine, peer, log, offsets, present=None, ctx: Context | None = No
     return SenderStep(mine_out, action[:nseg], drain[:nseg], split_hits(hits, hoffs, offs))
 
 
+@dataclass
+class SenderSteps:
+    """What sender_steps returns: per queued quACK (queue order) and per flow."""
+    mine_out: object      # CUDA int32 record tensor [nseg, 4 + t]: my quACKs after the flow's last stepped quACK
+    q_action: np.ndarray  # np.uint8 per quACK: SND_IDLE, SND_ADVANCED, the OR of the SND_RESET_* bits, or SND_UNSTEPPED
+    q_drain: np.ndarray   # np.uint64 per quACK: the log entries its step drops
+    stepped: np.ndarray   # np.uint32 per flow: quACKs consumed, the resetting one included
+    drain: np.ndarray     # np.uint64 per flow: the sum of its q_drain (drain_segments / update_segments)
+    missing: list         # per quACK, the positions to retransmit, local to the flow's segment, ascending
+    q_offsets: np.ndarray  # np.uint64 [nseg + 1]: the queue's CSR index by flow
+
+
+def sender_steps(mine, queue, q_offsets, log, offsets, ctx: Context | None = None) -> SenderSteps:
+    """listen_for_quacks_power_sum (media_client.rs:223-323) for a batch of
+    flows with EVERY queued quACK of a flow stepped, one after the other, in one
+    device call (qk_u32_sender_steps_segments_device).  `mine`: my quACK per
+    flow; `queue`: the received quACKs grouped by flow, in arrival order within
+    a flow, `q_offsets` their CSR index (nseg + 1 ints, q_offsets[0] == 0) —
+    what ingest_wire_queue returns (both record batches: a list of
+    PowerSumQuackU32 of one threshold, uploaded here, or a CUDA int32 record
+    tensor); `log` / `offsets` as sender_step takes them.  Per flow the loop of
+    sender_step runs over its quACKs on a log that each ADVANCED step shortens
+    (by an offset: the log is not moved) and stops at the first reset: the
+    quACKs behind it stay SND_UNSTEPPED, for the caller to drop (the reset
+    fired) or to pass again (the debounce held it back)."""
+    r_mine = Records.parse(mine, PowerSumQuackU32)
+    r_mine.need_threshold("mine")
+    nseg, t = r_mine.nseg, r_mine.t
+    r_queue = Records.parse(queue, PowerSumQuackU32, threshold=t)
+    if r_queue.t != t:
+        raise QuackError(QK_E_MISMATCH, "mine and queue of different thresholds")
+    qoffs, _ = csr(q_offsets, "mine", nseg, r_queue.nseg)
+    nq = int(qoffs[-1])
+    ctx = ctx or get_context(r_mine.dev or 0)
+    d_mine = r_mine.to_device(ctx, "mine")
+    d_queue = r_queue.to_device(ctx, "queue") if r_queue.nseg else None
+    torch = need_torch()
+    device = d_mine.device
+    if d_queue is not None and d_queue.device != device:
+        raise ValueError("mine and queue on different devices")
+    d_log = _device_array(log, 32)
+    if d_log is None:
+        log = uint_on_device(log, device, "log")
+        d_log = _device_array(log, 32)
+    lptr, n, _, stream = d_log
+    offs, _ = csr(offsets, "mine", nseg, n)
+    mine_out = torch.empty((nseg, 4 + t), dtype=torch.int32, device=device)
+    q_action = np.zeros(max(nq, 1), dtype=np.uint8)
+    q_drain = np.zeros(max(nq, 1), dtype=np.uint64)
+    stepped = np.zeros(max(nseg, 1), dtype=np.uint32)
+    drain = np.zeros(max(nseg, 1), dtype=np.uint64)
+    hoffs = np.zeros(nq + 1, dtype=np.uint64)
+
+    def attempt(cap):
+        hits = np.empty(max(cap, 1), dtype=np.uint64)
+        nh = C.c_size_t()
+        rc = lib().qk_u32_sender_steps_segments_device(
+            ctx.handle, d_mine.data_ptr(), d_queue.data_ptr() if d_queue is not None else None, ptr(qoffs), lptr,
+            ptr(offs), nseg, t, mine_out.data_ptr(), ptr(q_action), ptr(q_drain), ptr(stepped), ptr(drain), ptr(hits),
+            cap, ptr(hoffs), C.byref(nh), stream)
+        return rc, nh.value, hits
+    hits = retry_capacity(attempt, max(1024, 4 * nseg), "sender_steps")
+    # the segment start of every quACK's flow (q_offsets[0] == 0: the library refuses anything else)
+    first = np.repeat(offs[:-1], (qoffs[1:] - qoffs[:-1]).astype(np.int64)) if nseg else offs[:0]
+    return SenderSteps(mine_out, q_action[:nq], q_drain[:nq], stepped[:nseg], drain[:nseg],
+                       split_hits(hits, hoffs, first), qoffs)
+
+
 def drain_segments(log, offsets, drain, aux=None, ctx: Context | None = None):
     """seqno_ids.drain(..idx+1) (media_client.rs:298,316) for all flows on the
     device (qk_u32_log_drain_segments_device): segment g of the result is
@@ -805,13 +875,93 @@ class DeviceSenderLog:
                 at += c
         return SenderLogStep(action, fired, reason, retransmit)
 
-    def on_wire(self, wire, lens, flow, now: float = 0.0):
+    def on_quack_queue(self, queue, q_offsets, now: float = 0.0) -> SenderLogStep:
+        """on_quack(q, now) on flow g for every queued quACK q of the flow, in
+        queue order (sender_steps; `queue` / `q_offsets` as ingest_wire_queue
+        returns them): flow g ends exactly as a QuackReceiver given them one
+        after the other with this `now`.  A reset that fires clears the flow
+        and drops the rest of its queue (the reference answers each of them
+        with a reset the debounce holds back: nothing changes); one the
+        debounce holds back is followed by a further step on the flow's
+        unstepped tail, from the quACK the prefix insert left.  Per flow:
+        action = its last stepped action that was not IDLE, reset_reason = its
+        last reset's, retransmit = the seqnos of all its hits, in order."""
+        torch = need_torch()
+        nf, t = self.nflows, self.threshold
+        qoffs, _ = csr(q_offsets, "the flows", nf)
+        r_queue = Records.parse(queue, PowerSumQuackU32, threshold=t)
+        if int(qoffs[0]) != 0 or int(qoffs[-1]) > r_queue.nseg or np.any(qoffs[1:] < qoffs[:-1]):
+            raise QuackError(QK_E_INVAL, "on_quack_queue: q_offsets is no CSR index of queue")
+        d_queue = (r_queue.to_device(self._ctx, "queue") if r_queue.nseg
+                   else torch.empty((0, 4 + t), dtype=torch.int32, device=self._device))
+        action = np.zeros(nf, dtype=np.uint8)
+        fired = np.zeros(nf, dtype=bool)
+        reason = [() for _ in range(nf)]
+        retransmit = [[] for _ in range(nf)]
+        lo, hi = qoffs[:-1].astype(np.int64), qoffs[1:].astype(np.int64)   # what is left of each flow's queue
+        last = self.last_quack_reset
+        whole = True
+        while True:
+            self.flush()            # the drain pending from before, or the previous pass's: the tails step a moved log
+            k = hi - lo
+            if whole:
+                sub, soffs = d_queue, qoffs
+            else:
+                idx = np.concatenate([np.arange(a, b) for a, b in zip(lo.tolist(), hi.tolist()) if b > a])
+                sub = d_queue[torch.from_numpy(idx).to(self._device)].contiguous()
+                soffs = np.concatenate([[0], np.cumsum(k)]).astype(np.uint64)
+            whole = False
+            res = sender_steps(self.mine, sub, soffs, self.log, self.offsets, ctx=self._ctx)
+            self.mine = res.mine_out
+            drain = res.drain.copy()
+            # the seqnos at the hit positions: the only log values that cross to the host
+            counts = [len(m) for m in res.missing]
+            at = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+            vals = []
+            if at[-1]:
+                flow_of = np.repeat(np.arange(nf), k)
+                pos = np.concatenate([np.asarray(m, dtype=np.int64) + int(self.offsets[flow_of[q]])
+                                      for q, m in enumerate(res.missing) if m])
+                vals = self.seqnos[torch.from_numpy(pos).to(self._device)].cpu().numpy().view(np.uint32).tolist()
+            cleared = []
+            for g in np.flatnonzero(k).tolist():
+                a, s = int(soffs[g]), int(res.stepped[g])
+                retransmit[g] += vals[at[a]:at[a + s]]
+                lo[g] += s
+                for act in res.q_action[a:a + s].tolist():
+                    if act == SND_IDLE:
+                        continue
+                    action[g] = act
+                    if act == SND_ADVANCED:
+                        last[g] = np.nan                                            # :280-283
+                        continue
+                    reason[g] = ((act & SND_RESET_REORDERED) != 0, (act & SND_RESET_RETX) != 0,
+                                 (act & SND_RESET_EXCEEDS) != 0)
+                    if np.isnan(last[g]) or now > last[g] + self.reset_debounce_s:  # :267-276
+                        fired[g] = True
+                        last[g] = now
+                        drain[g] = self.offsets[g + 1] - self.offsets[g]
+                        lo[g] = hi[g]
+                        cleared.append(g)
+            if cleared:
+                self.mine[torch.from_numpy(np.asarray(cleared, dtype=np.int64)).to(self._device)] = self._fresh
+            self._pending = drain if drain.any() else None
+            if not np.any(hi > lo):
+                break
+        return SenderLogStep(action, fired, reason, retransmit)
+
+    def on_wire(self, wire, lens, flow, now: float = 0.0, every: bool = False):
         """A batch of received datagrams (ingest_wire: image i in row i of the
         CUDA uint8 tensor `wire`, lens[i] bytes, of flow flow[i]) through
         on_quacks: the newest accepted quACK of every flow is stepped, no
-        per-flow host work in between.  Returns (SenderLogStep, status), status
-        as ingest_wire gives it."""
+        per-flow host work in between.  every=True: through ingest_wire_queue
+        and on_quack_queue instead, every accepted quACK of a flow stepped in
+        arrival order.  Returns (SenderLogStep, status), status as the ingest
+        gives it."""
         nf = self.nflows
+        if every:
+            queue, q_offsets, status, _ = ingest_wire_queue(wire, lens, flow, nf, self.threshold, ctx=self._ctx)
+            return self.on_quack_queue(queue, q_offsets, now=now), status
         if self._peer is None or self._peer.shape[0] != nf:
             old = self._peer
             self._peer = self._fresh.unsqueeze(0).expand(nf, -1).contiguous()
@@ -1218,6 +1368,41 @@ def ingest_wire(wire, lens, flow, nflows: int, threshold: int, peer=None, ctx: C
         flow.data_ptr() if n else None, n, t, nflows, peer.data_ptr() if nflows else None,
         present.data_ptr() if nflows else None, ptr(status), C.byref(acc), stream_of(wire)), "ingest_wire")
     return peer, present, status[:n], acc.value
+
+
+def ingest_wire_queue(wire, lens, flow, nflows: int, threshold: int, ctx: Context | None = None):
+    """ingest_wire with nothing superseded (qk_u32_wire_ingest_queue_device):
+    every accepted datagram becomes a record of the queue, grouped by flow and,
+    within a flow, in arrival order.  Arguments as ingest_wire's.  Returns
+    (queue, q_offsets, status, n_accepted): the CUDA int32 record tensor
+    [n_accepted, 4 + t], its CSR index by flow (np.uint64 [nflows + 1]) — both
+    as sender_steps takes them — and `status` as ingest_wire gives it, without
+    QK_WIRE_SUPERSEDED."""
+    ctx = _context(ctx, wire)
+    torch = need_torch()
+    nflows, t = int(nflows), int(threshold)
+    if not (isinstance(wire, torch.Tensor) and wire.is_cuda and wire.dtype == torch.uint8 and wire.dim() == 2
+            and wire.is_contiguous()):
+        raise TypeError("wire must be a contiguous CUDA uint8 tensor [n, stride]")
+    n, stride = wire.shape
+    device = wire.device
+    if uint_len(lens, "lens") != n or uint_len(flow, "flow") != n:
+        raise ValueError("lens and flow must hold one entry per datagram")
+    lens = uint_on_device(lens, device, "lens")
+    flow = uint_on_device(flow, device, "flow")
+    q_offsets = np.zeros(nflows + 1, dtype=np.uint64)
+    status = np.zeros(max(n, 1), dtype=np.int32)
+
+    def attempt(cap):
+        queue = torch.empty((cap, 4 + t), dtype=torch.int32, device=device)
+        acc = C.c_size_t()
+        rc = lib().qk_u32_wire_ingest_queue_device(
+            ctx.handle, wire.data_ptr() if n else None, max(int(stride), 1), lens.data_ptr() if n else None,
+            flow.data_ptr() if n else None, n, t, nflows, queue.data_ptr() if cap else None, cap, ptr(q_offsets),
+            ptr(status), C.byref(acc), stream_of(wire))
+        return rc, acc.value, (queue, acc.value)
+    queue, m = retry_capacity(attempt, n, "ingest_wire_queue")   # every datagram accepted: n records
+    return queue[:m], q_offsets, status[:n], m
 
 
 class DeviceFlowQuacks:
