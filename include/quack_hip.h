@@ -325,6 +325,58 @@ int qk_u32_snapshot_segments_device(qk_ctx *ctx, const uint8_t *d_base, const ui
                                     uint32_t *d_snap_seg_out, uint64_t *d_snap_pos_out,
                                     uint32_t *d_snap_arrival_out, size_t cap, uint64_t *snap_offsets,
                                     size_t *n_snap, uint8_t *d_final_out, void *stream);
+/* The proxy's frequency loop on captured packets
+ * (sidekick_multi.rs:240-287, start_sidekick_multi_frequency_pkts), against a
+ * flow table held by AddrKey in device memory: qk_u32_encode_flows_device's
+ * packet front joined with qk_u32_snapshot_segments_device's every-crossing
+ * walk.  For records i = 0 .. n - 1 in order, classified exactly as
+ * qk_u32_encode_flows_device classifies them (skip on direction, protocol or
+ * not-UDP; then Reset if key[6..12] == my_addr; then skip on a length !=
+ * QK_BUFFER_SIZE; else Insert of (key, id)):
+ *   Reset   the table becomes empty, every flow goes (:263-266);
+ *   Insert  the flow's quACK (the table's, or a fresh qk_u32_init(threshold))
+ *           takes the id; when its new count is a multiple of frequency_pkts,
+ *           on the wrapping u32 as in qk_u32_snapshot_segments_device (a count
+ *           that wraps to 0 emits), packet i emits a snapshot (:271-283).
+ * Table in: d_keys[n_table] strictly ascending in memcmp order with d_sk record
+ * j (qk_u32_size(threshold) bytes) the quACK of key j: a flow array as
+ * qk_u32_flows_merge_device keeps it.  Outputs:
+ *   the snapshots in ascending i, the reference's send order: d_snap_out row r
+ *   the qk_u32 record of the flow right after its packet (last_value the raw
+ *   id), d_snap_key_out[r] its key, d_snap_index_out[r] = i.  Snapshots emitted
+ *   in front of a Reset inside the batch are part of the output; their sums
+ *   build on the table of their epoch: the input table in front of the first
+ *   Reset, an empty one behind each Reset;
+ *   the table after the last packet, d_keys_out / d_sk_out (*n_table_out rows,
+ *   keys strictly ascending): the input table united with the batch when the
+ *   batch holds no Reset (a row the batch touched replaced by its end-of-batch
+ *   record, the others copied), else only the flows inserted behind the last
+ *   Reset;
+ *   stats as qk_u32_encode_flows_device gives them (discarded: the Inserts in
+ *   front of the last Reset; they did emit).  With frequency_pkts == 1,
+ *   *n_snap == inserted + discarded.
+ * All d_* arguments are device memory of ctx's GPU, 4-byte aligned (d_bufs:
+ * any alignment); my_addr (NULL: no packet resets), n_table_out, n_snap and
+ * stats are host memory.  NULL ctx -> QK_E_INVAL before any other check;
+ * threshold 0 or > 1024 -> QK_E_THRESHOLD; frequency_pkts == 0, a stride
+ * outside 67 .. 512, n >= 2^32, n_table >= 2^31, a host pointer where a device
+ * one is required or the reverse, a misaligned array, an output range
+ * overlapping an input or another output, input keys not strictly ascending
+ * (found on the device) -> QK_E_INVAL; a table record of another threshold ->
+ * QK_E_MISMATCH; table_cap or snap_cap too small -> QK_E_CAPACITY with
+ * *n_table_out, *n_snap and stats set and no output array written (a repeat
+ * with larger caps gives the same result; a call whose caps are both at least
+ * the batch's Inserts never needs one); n == 0 -> QK_OK, the table copied, no
+ * snapshots.  A batch with Resets runs the chain once per epoch between them
+ * (Resets are rare: one per receiver request, media_client.rs:272).
+ * Synchronous on `stream`. */
+int qk_u32_snapshot_flows_device(qk_ctx *ctx, const uint8_t *d_bufs, size_t n, size_t stride,
+                                 const qk_pkt_meta *d_meta, const uint8_t my_addr[6], uint32_t threshold,
+                                 uint32_t frequency_pkts, const qk_flow_key *d_keys, const uint8_t *d_sk,
+                                 size_t n_table, qk_flow_key *d_keys_out, uint8_t *d_sk_out, size_t table_cap,
+                                 size_t *n_table_out, uint8_t *d_snap_out, qk_flow_key *d_snap_key_out,
+                                 uint32_t *d_snap_index_out, size_t snap_cap, size_t *n_snap, qk_pkt_stats *stats,
+                                 void *stream);
 
 /* ------------------------------------------------------------------------
  * Decode-missing root test.  Replaces media_client.rs:306-313:

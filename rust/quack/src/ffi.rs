@@ -205,6 +205,16 @@ extern "C" {
                                            d_snap_seg_out: *mut u32, d_snap_pos_out: *mut u64,
                                            d_snap_arrival_out: *mut u32, cap: usize, snap_offsets: *mut u64,
                                            n_snap: *mut usize, d_final_out: *mut u8, stream: *mut c_void) -> c_int;
+    // the proxy's frequency loop on captured packets against the flow table held by AddrKey
+    // (sidekick_multi.rs:240-287): every due quACK in send order, the table after the batch
+    pub fn qk_u32_snapshot_flows_device(ctx: *mut qk_ctx, d_bufs: *const u8, n: usize, stride: usize,
+                                        d_meta: *const qk_pkt_meta, my_addr: *const u8, threshold: u32,
+                                        frequency_pkts: u32, d_keys: *const qk_flow_key, d_sk: *const u8,
+                                        n_table: usize, d_keys_out: *mut qk_flow_key, d_sk_out: *mut u8,
+                                        table_cap: usize, n_table_out: *mut usize, d_snap_out: *mut u8,
+                                        d_snap_key_out: *mut qk_flow_key, d_snap_index_out: *mut u32,
+                                        snap_cap: usize, n_snap: *mut usize, stats: *mut qk_pkt_stats,
+                                        stream: *mut c_void) -> c_int;
 
     // root test / decode
     pub fn qk_u32_root_test_device(ctx: *mut qk_ctx, coeffs: *const u32, d: u32, d_log: *const u32, n: usize,

@@ -692,6 +692,57 @@ pub unsafe fn flows_merge_device(ctx: &Context, a: DeviceFlows, b: DeviceFlows, 
     Ok(n_out)
 }
 
+/// Where [`snapshot_flows_device`] writes: the table after the batch (`table_cap`
+/// rows) and the emitted quACKs in send order (`snap_cap` rows: record, key and
+/// packet index of each).  All device memory, apart from the inputs.
+#[derive(Clone, Copy)]
+pub struct FlowSnapshotsOut {
+    pub keys: *mut ffi::qk_flow_key,
+    pub sketches: *mut u8,
+    pub table_cap: usize,
+    pub snap: *mut u8,
+    pub snap_keys: *mut ffi::qk_flow_key,
+    pub snap_index: *mut u32,
+    pub snap_cap: usize,
+}
+
+/// What [`snapshot_flows_device`] found: rows of the new table, snapshots
+/// emitted, and the batch's packet counts.  On `QK_E_CAPACITY` the first two
+/// are the sizes a repeat needs.
+pub struct FlowSnapshotCounts {
+    pub n_table: usize,
+    pub n_snap: usize,
+    pub stats: ffi::qk_pkt_stats,
+}
+
+/// `start_sidekick_multi_frequency_pkts` over a batch of captured packets
+/// (`sidekick_multi.rs:256-286`) against the flow table `table`, on the device:
+/// per packet the filters and the `AddrKey`, `sc.insert(addr_key, id)`, a send
+/// whenever `quack.count() % frequency_pkts == 0`, and `sc =
+/// SidekickMulti::new(..)` on a Reset packet (`:263-266`).  The quACKs come out
+/// in send order, those sent before a Reset inside the batch included.
+/// Returns the counts and the status: `Ok` also for `QK_E_CAPACITY`, where
+/// nothing was written and the counts say what to allocate.
+///
+/// # Safety
+/// `d_bufs` (n * stride bytes), `d_meta` (n records or null), `table` and every
+/// pointer of `out` must be device memory of `ctx`'s GPU of the stated size.
+pub unsafe fn snapshot_flows_device(ctx: &Context, d_bufs: *const u8, n: usize, stride: usize,
+                                    d_meta: *const ffi::qk_pkt_meta, my_addr: Option<[u8; 6]>, threshold: u32,
+                                    frequency_pkts: u32, table: DeviceFlows, out: FlowSnapshotsOut,
+                                    stream: *mut c_void) -> Result<(FlowSnapshotCounts, bool)> {
+    let addr = my_addr.as_ref().map_or(ptr::null(), |a| a.as_ptr());
+    let (mut n_table, mut n_snap, mut stats) = (0usize, 0usize, ffi::qk_pkt_stats::default());
+    let rc = ffi::qk_u32_snapshot_flows_device(ctx.raw, d_bufs, n, stride, d_meta, addr, threshold, frequency_pkts,
+                                               table.keys, table.sketches, table.n, out.keys, out.sketches,
+                                               out.table_cap, &mut n_table, out.snap, out.snap_keys, out.snap_index,
+                                               out.snap_cap, &mut n_snap, &mut stats, stream);
+    if rc != ffi::QK_E_CAPACITY {
+        check(rc)?;
+    }
+    Ok((FlowSnapshotCounts { n_table, n_snap, stats }, rc == ffi::QK_OK))
+}
+
 /// `diff_quack = my_quack.clone(); diff_quack.sub_assign(quack)`
 /// (`media_client.rs:295-296`) for every flow of `a` (mine) against `b` (the
 /// peer's): `a.n` records into `diffs_out` in `a`'s key order, ready for

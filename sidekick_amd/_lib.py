@@ -121,6 +121,8 @@ SIGNATURES = {
     "qk_u32_log_update_segments_device": (C.c_int, [vp, vp, vp, u64p, u64p, sz, vp, vp, vp, sz, vp, vp, sz, u64p, vp]),
     "qk_u32_snapshot_segments_device": (C.c_int, [vp, vp, vp, vp, u64p, sz, C.c_uint32, C.c_uint32, vp, vp, vp, vp, sz,
                                                   u64p, szp, vp, vp]),
+    "qk_u32_snapshot_flows_device": (C.c_int, [vp, vp, sz, sz, vp, vp, C.c_uint32, C.c_uint32, vp, vp, sz, vp, vp, sz, szp,
+                                               vp, vp, vp, sz, szp, vp, vp]),
     "qk_u32_flows_merge_device": (C.c_int, [vp, vp, vp, sz, vp, vp, sz, C.c_uint32, C.c_uint32, vp, vp, vp, sz, szp,
                                             vp]),
     "qk_u32_flows_diff_device": (C.c_int, [vp, vp, vp, sz, vp, vp, sz, C.c_uint32, vp, szp, vp]),

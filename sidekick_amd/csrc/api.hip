@@ -371,7 +371,7 @@ int qk_ctx_create(int device, qk_ctx **out) {
     // work-item buffer (1 MiB) allocated
     uint64_t pageable[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (ensure_items(ctx, (size_t)1 << 20) || warm_api(ctx->stream) || warm_encode(ctx->stream) || warm_decode(ctx->stream) ||
-        warm_packets(ctx->stream) || warm_flows(ctx->stream) || warm_segments(ctx->stream) || warm_segdecode(ctx->stream) || warm_sender(ctx->stream) || warm_sendersteps(ctx->stream) || warm_senderlog(ctx->stream) || warm_snapshots(ctx->stream) ||
+        warm_packets(ctx->stream) || warm_flows(ctx->stream) || warm_segments(ctx->stream) || warm_segdecode(ctx->stream) || warm_sender(ctx->stream) || warm_sendersteps(ctx->stream) || warm_senderlog(ctx->stream) || warm_snapshots(ctx->stream) || warm_pktsnap(ctx->stream) ||
         warm_flowtable(ctx->stream) || warm_wire(ctx->stream) || warm_comm(ctx->stream) ||
         hipMemsetAsync(ctx->d_small, 0, SMALL_DEV_WORDS * sizeof(uint64_t), ctx->stream) != hipSuccess ||
         hipMemcpyAsync(ctx->d_small, pageable, sizeof pageable, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||

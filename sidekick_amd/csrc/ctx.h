@@ -188,6 +188,7 @@ int warm_sender(hipStream_t s);
 int warm_sendersteps(hipStream_t s);
 int warm_senderlog(hipStream_t s);
 int warm_snapshots(hipStream_t s);
+int warm_pktsnap(hipStream_t s);
 int warm_flowtable(hipStream_t s);
 int warm_wire(hipStream_t s);
 int warm_comm(hipStream_t s);

@@ -52,6 +52,7 @@
 #include "bsgs.h"
 #include "ctx.h"
 #include "field.h"
+#include "flowfront.h"
 #include "radix.h"
 #include "records.h"
 #include "segments.h"
@@ -74,11 +75,7 @@ static_assert(sizeof(qk_u32) == 16, "qk_u32 header is 4 words (k_flow_finalize_b
 // another (no intra-wave spin hazard): the slot belongs to the key whose w1
 // lands first, and every lane decides on final values only, so all lanes of
 // one key stop at the same slot.
-struct alignas(16) FlowSlot {
-    uint64_t w0, w1;
-};
-constexpr uint32_t SLOT_NONE = 0xFFFFFFFFu;
-constexpr uint64_t FT_OVERFLOW = 1;   // counters[3] flag
+// (FlowSlot, SLOT_NONE, FT_OVERFLOW: flowfront.h)
 
 __device__ __forceinline__ uint64_t ft_w0(uint64_t src, uint64_t dst) { return (src + 1) | ((dst >> 33) << 49); }
 __device__ __forceinline__ uint64_t ft_w1(uint64_t dst) { return (dst & ((1ull << 33) - 1)) | (1ull << 40); }
@@ -221,6 +218,7 @@ __global__ __launch_bounds__(REC_TILE) void k_flow_extract(const uint8_t *__rest
                   ((uint64_t)rec[33] << 16) | ((uint64_t)rec[36] << 8) | (uint64_t)rec[37];
             if (dst == my_key_lo) {
                 cls = 2;
+                id = FLOW_ID_RESET;   // (slot, id) tells a Reset from a skipped packet
                 my_rst = i + 1;
             } else if (m.len == QK_BUFFER_SIZE) {
                 cls = 1;
@@ -670,6 +668,123 @@ static uint64_t next_pow2(uint64_t v) {
 
 using namespace qk;
 
+// ---- the packet front's host drivers (flowfront.h) -------------------------
+static RsPlan extract_plan(const qk_ctx *ctx, uint64_t pn);
+
+void qk::flow_front_init(const qk_ctx *ctx, uint64_t n, FlowFront &ff) {
+    ff.cmax = std::min<uint64_t>(next_pow2(2 * n + 2), 1ull << 31);
+    // table slots per expected flow (2 / 8 measured slower at 1e6 / 1e4 flows,
+    // profiles/r02/s3/flows_load/, profiles/r05/flows_nd/)
+    const uint64_t spf = 4;
+    ff.C = std::min<uint64_t>(ff.cmax, next_pow2(std::max<uint64_t>(4096, spf * (uint64_t)ctx->flow_hint)));
+}
+
+int qk::flow_extract(qk_ctx *ctx, hipStream_t s, const uint8_t *pb, uint64_t pn, size_t stride,
+                     const qk_pkt_meta *pm, uint64_t my_key, uint32_t *slots, uint32_t *ids,
+                     unsigned long long *counters, uint32_t *hist, uint32_t hg, FlowFront &ff) {
+    ff.xpl = extract_plan(ctx, pn);
+    uint64_t &C = ff.C;
+    for (;;) {
+        {
+            Carve probe{nullptr};
+            probe.take<FlowSlot>(C);
+            probe.take<uint32_t>(C);
+            if (int e = ensure_flow(ctx, 2, probe.off, s)) return e;
+            Carve cv{(char *)ctx->d_flow[2]};
+            ff.tab = cv.take<FlowSlot>(C);
+            ff.rank_of_slot = cv.take<uint32_t>(C);
+        }
+        if (hipMemsetAsync(ff.tab, 0, C * sizeof(FlowSlot), s) != hipSuccess ||
+            hipMemsetAsync(counters, 0, FLOW_COUNTERS * 8, s) != hipSuccess ||
+            (hist &&
+             hipMemsetAsync(hist, 0, (size_t)rsort::R * ((ff.xpl.nwg + hg - 1) / hg) * 4, s) != hipSuccess))
+            return QK_E_HIP;
+        const uint32_t probe_limit = C == ff.cmax ? (uint32_t)C - 1 : 64u;   // load <= 1/4 when sized from the hint
+        // the by-slot sort's first digit (8-bit variants): its passes and
+        // width as rs_sort_k cuts bits(C - 1)
+        const int cb = bit_width32((uint32_t)(C - 1)), np = (cb + 7) / 8, dd = (cb + np - 1) / np;
+        if (pn)
+            hipLaunchKernelGGL(k_flow_extract, dim3(ff.xpl.nwg), dim3(REC_TILE), (size_t)REC_TILE * stride + 32, s, pb,
+                               pn, (uint32_t)stride, pm, my_key, ff.xpl.chunk, ff.tab, (uint32_t)(C - 1), probe_limit,
+                               slots, ids, counters, (1u << dd) - 1, hist, hg);
+        // the counters into pinned memory (an async copy to pageable memory
+        // would hold the host until the extract ends); flow_ev[0]: the
+        // table is complete (the key-ranking branch waits for it)
+        if (hipGetLastError() != hipSuccess ||
+            hipMemcpyAsync(ctx->h_flow, counters, FLOW_COUNTERS * 8, hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipEventRecord(ctx->flow_ev[2], s) != hipSuccess || hipEventRecord(ctx->flow_ev[0], s) != hipSuccess)
+            return QK_E_HIP;
+        if (hipEventSynchronize(ctx->flow_ev[2]) != hipSuccess) return QK_E_HIP;
+        std::copy(ctx->h_flow, ctx->h_flow + FLOW_COUNTERS, ff.hc);
+        if (!(ff.hc[3] & FT_OVERFLOW)) return QK_OK;
+        if (C == ff.cmax) return QK_E_NOMEM;   // > 2^31 flows: no table size left
+        C = std::min<uint64_t>(ff.cmax, next_pow2(std::max<uint64_t>(16 * C, 4 * ff.hc[2])));
+    }
+}
+
+void qk::FlowKeyBuf::take(Carve &c, const qk_ctx *ctx, uint64_t C, uint32_t nf) {
+    // (key word, slot) arrays of the flow-key sort, taken in this order:
+    // each key array followed by its value array holds nf pairs (radix.h)
+    kA = c.take<uint32_t>(nf); vA = c.take<uint32_t>(nf); kB = c.take<uint32_t>(nf); vB = c.take<uint32_t>(nf);
+    used = c.take<uint32_t>(nf); sl3 = c.take<uint32_t>(nf);
+    nsel = c.take<uint32_t>(2);
+    // the occupied-slot compaction (unb workgroups of uchunk slots) and the
+    // flow-key sort's scan scratch
+    unb = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(1024, (C + 4095) / 4096));
+    uchunk = ((C + unb - 1) / unb + 255) & ~(uint64_t)255;
+    wcnt = c.take<uint32_t>(unb);
+    krs.take(c, rs_plan(ctx, nf, RS_WGPC_MAX).nwg, nf);
+}
+
+int qk::flow_key_order(qk_ctx *ctx, hipStream_t s2, const FlowFront &ff, uint32_t nf, const FlowKeyBuf &kb,
+                       const uint32_t **sorted) {
+    const uint32_t fblocks = (nf + 255) / 256;
+    // the occupied slots in slot order
+    hipLaunchKernelGGL(k_used_count, dim3(kb.unb), dim3(256), 0, s2, ff.tab, ff.C, kb.uchunk, kb.wcnt);
+    hipLaunchKernelGGL(k_used_write, dim3(kb.unb), dim3(256), 0, s2, ff.tab, ff.C, kb.uchunk, kb.wcnt, kb.used, kb.nsel);
+    if (hipGetLastError() != hipSuccess) return QK_E_HIP;
+    // ... in AddrKey order: one workgroup's rank sort for few flows,
+    // else an LSD radix sort of (key word, slot) pairs over the key's
+    // three 32-bit words (the next word gathered through the slots)
+    *sorted = kb.sl3;
+    if (nf <= KR_MAX) {
+        hipLaunchKernelGGL(k_key_rank_small, dim3(1), dim3(1024), 0, s2, ff.tab, kb.used, nf, kb.sl3);
+        if (hipGetLastError() != hipSuccess) return QK_E_HIP;
+    } else {
+        for (int q = 0; q < 3; ++q) {
+            hipLaunchKernelGGL(k_slot_word, dim3(fblocks), dim3(256), 0, s2, ff.tab, q ? kb.vA : kb.used, nf, q, kb.kA,
+                               q ? (uint32_t *)nullptr : kb.vA);
+            if (hipGetLastError() != hipSuccess) return QK_E_HIP;
+            int where = 1;
+            if (int e = rs_sort_k<256, 16, RS_WGPC_MAX>(ctx, kb.kA, kb.vA, kb.kB, kb.vB, nf, 32, kb.krs, s2, where))
+                return e;
+            if (where != 0) return QK_E_HIP;   // four passes: the result is back in (kA, vA)
+        }
+        *sorted = kb.vA;
+    }
+    return QK_OK;
+}
+
+int qk::flow_rank_keys(hipStream_t s, const FlowFront &ff, const uint32_t *sorted, uint32_t nf, uint8_t *d_keys) {
+    hipLaunchKernelGGL(k_slot_rank, dim3((nf + 255) / 256), dim3(256), 0, s, ff.tab, sorted, nf, ff.rank_of_slot, d_keys);
+    return hipGetLastError() == hipSuccess ? QK_OK : QK_E_HIP;
+}
+
+int qk::flow_slots_to_ranks(const qk_ctx *ctx, hipStream_t s, uint32_t *key, const FlowFront &ff, uint64_t n,
+                            uint32_t nf) {
+    const uint32_t gb = (uint32_t)std::min<uint64_t>((n + 255) / 256, (uint64_t)ctx->num_cus * 8);
+    if (!gb) return QK_OK;
+    hipLaunchKernelGGL(k_slot_to_rank, dim3(gb), dim3(256), 0, s, key, ff.rank_of_slot, n, nf);
+    return hipGetLastError() == hipSuccess ? QK_OK : QK_E_HIP;
+}
+
+int qk::flow_rank_offsets(const qk_ctx *ctx, hipStream_t s, const uint32_t *key, uint64_t inserted, uint32_t nf,
+                          uint64_t *d_offs) {
+    const uint32_t ob = (uint32_t)std::min<uint64_t>((inserted + 255) / 256, (uint64_t)ctx->num_cus * 8);
+    hipLaunchKernelGGL(k_rank_offsets, dim3(std::max(ob, 1u)), dim3(256), 0, s, key, inserted, nf, d_offs);
+    return hipGetLastError() == hipSuccess ? QK_OK : QK_E_HIP;
+}
+
 // k_flow_extract's chunking of pn packets: >= 4 tiles per workgroup, enough
 // workgroups to cover the chip (FLOW_WGPC workgroups per CU; 4, 6, 8, 12
 // measured, 12 best at 1e4 and 1e6 flows).  With the fused first-digit
@@ -697,10 +812,7 @@ extern "C" int qk_u32_encode_flows_device(qk_ctx *ctx, const uint8_t *d_bufs, si
         return QK_OK;
     }
     if (!is_device_ptr(d_bufs) || (d_meta && !is_device_ptr(d_meta))) return QK_E_INVAL;
-    uint64_t my_key = ~0ull; // no own address: no packet is a reset
-    if (my_addr)
-        my_key = ((uint64_t)my_addr[0] << 40) | ((uint64_t)my_addr[1] << 32) | ((uint64_t)my_addr[2] << 24) |
-                 ((uint64_t)my_addr[3] << 16) | ((uint64_t)my_addr[4] << 8) | (uint64_t)my_addr[5];
+    const uint64_t my_key = flow_my_key(my_addr); // no own address: no packet is a reset
     std::lock_guard<std::mutex> g(ctx->mu);
     QK_HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = pick_stream(ctx, stream);
@@ -710,11 +822,9 @@ extern "C" int qk_u32_encode_flows_device(qk_ctx *ctx, const uint8_t *d_bufs, si
     // copies (16 B per packet), counters, the grouping sort's scan scratch.
     // Arena 2: the flow table (C slots) and slot -> rank.  Arena 1, per flow:
     // see below.
-    const uint64_t cmax = std::min<uint64_t>(next_pow2(2 * (uint64_t)n + 2), 1ull << 31);
-    // table slots per expected flow (2 / 8 measured slower at 1e6 / 1e4 flows,
-    // profiles/r02/s3/flows_load/, profiles/r05/flows_nd/)
-    const uint64_t spf = 4;
-    uint64_t C = std::min<uint64_t>(cmax, next_pow2(std::max<uint64_t>(4096, spf * (uint64_t)ctx->flow_hint)));
+    FlowFront ff;
+    flow_front_init(ctx, n, ff);
+    uint64_t &C = ff.C;
     // the grouping sort's chunk counts: its own plan's, or the extract's
     const uint32_t rs_nwg = std::max(rs_plan(ctx, n, RS_WGPC_MAX).nwg, extract_plan(ctx, n).nwg);
     uint32_t *slots = nullptr, *ids = nullptr, *key_s = nullptr, *id_s = nullptr;
@@ -738,57 +848,17 @@ extern "C" int qk_u32_encode_flows_device(qk_ctx *ctx, const uint8_t *d_bufs, si
     // before it is wiped (sidekick_multi.rs:205,265): the pass reruns over the
     // packets after the last reset with an empty table.
     int rc = QK_OK;
-    FlowSlot *tab = nullptr;
-    uint32_t *rank_of_slot = nullptr;
-    uint64_t hc[5] = {0, 0, 0, 0, 0};
-    RsPlan xpl{1, 4};   // the extract's chunking of the last pass 1
+    uint64_t *const hc = ff.hc;
     // the grouping sort's chunks when the extract counts its first digit: hg
     // consecutive extract chunks each (~RS_WGPC_MAX workgroups per CU: the
     // scatter's LDS allows 4; the extract's 12 per CU measured slower)
     const uint32_t hg = (FLOW_WGPC + RS_WGPC_MAX - 1) / RS_WGPC_MAX;
-    auto sort_plan = [&]() { return RsPlan{(xpl.nwg + hg - 1) / hg, xpl.chunk * hg}; };
+    auto sort_plan = [&]() { return RsPlan{(ff.xpl.nwg + hg - 1) / hg, ff.xpl.chunk * hg}; };
     // the extract writes the by-slot sort's first-digit counts (1e6 flows
     // 6.71 -> 6.61 ms, profiles/r05/check4/ab_fuse0.log)
     auto pass1 = [&](uint64_t p_from) -> int {
-        const uint64_t pn = n - p_from;
-        const uint8_t *pb = d_bufs + p_from * stride;
-        const qk_pkt_meta *pm = d_meta ? d_meta + p_from : nullptr;
-        xpl = extract_plan(ctx, pn);
-        for (;;) {
-            {
-                Carve probe{nullptr};
-                probe.take<FlowSlot>(C);
-                probe.take<uint32_t>(C);
-                if (int e = ensure_flow(ctx, 2, probe.off, s)) return e;
-                Carve cv{(char *)ctx->d_flow[2]};
-                tab = cv.take<FlowSlot>(C);
-                rank_of_slot = cv.take<uint32_t>(C);
-            }
-            if (hipMemsetAsync(tab, 0, C * sizeof(FlowSlot), s) != hipSuccess ||
-                hipMemsetAsync(counters, 0, 5 * 8, s) != hipSuccess ||
-                hipMemsetAsync(rs.cnt, 0, (size_t)rsort::R * sort_plan().nwg * 4, s) != hipSuccess)
-                return QK_E_HIP;
-            const uint32_t probe_limit = C == cmax ? (uint32_t)C - 1 : 64u;   // load <= 1/4 when sized from the hint
-            // the by-slot sort's first digit (8-bit variants): its passes and
-            // width as rs_sort_k cuts bits(C - 1)
-            const int cb = bit_width32((uint32_t)(C - 1)), np = (cb + 7) / 8, dd = (cb + np - 1) / np;
-            if (pn)
-                hipLaunchKernelGGL(k_flow_extract, dim3(xpl.nwg), dim3(REC_TILE), (size_t)REC_TILE * stride + 32, s,
-                                   pb, pn, (uint32_t)stride, pm, my_key, xpl.chunk, tab, (uint32_t)(C - 1), probe_limit,
-                                   slots, ids, counters, (1u << dd) - 1, rs.cnt, hg);
-            // the counters into pinned memory (an async copy to pageable memory
-            // would hold the host until the extract ends); flow_ev[0]: the
-            // table is complete (the key-ranking branch waits for it)
-            if (hipGetLastError() != hipSuccess ||
-                hipMemcpyAsync(ctx->h_flow, counters, 40, hipMemcpyDeviceToHost, s) != hipSuccess ||
-                hipEventRecord(ctx->flow_ev[2], s) != hipSuccess || hipEventRecord(ctx->flow_ev[0], s) != hipSuccess)
-                return QK_E_HIP;
-            if (hipEventSynchronize(ctx->flow_ev[2]) != hipSuccess) return QK_E_HIP;
-            std::copy(ctx->h_flow, ctx->h_flow + 5, hc);
-            if (!(hc[3] & FT_OVERFLOW)) return QK_OK;
-            if (C == cmax) return QK_E_NOMEM;   // > 2^31 flows: no table size left
-            C = std::min<uint64_t>(cmax, next_pow2(std::max<uint64_t>(16 * C, 4 * hc[2])));
-        }
+        return flow_extract(ctx, s, d_bufs + p_from * stride, n - p_from, stride, d_meta ? d_meta + p_from : nullptr,
+                            my_key, slots, ids, counters, rs.cnt, hg, ff);
     };
     rc = pass1(0);
     const uint64_t all_inserts = hc[0], resets = hc[1];
@@ -817,8 +887,8 @@ extern "C" int qk_u32_encode_flows_device(qk_ctx *ctx, const uint8_t *d_bufs, si
         // and keys, offsets, and the flow-key sort buffers
         const size_t rec = qk_u32_size(T);
         uint64_t *d_offs = nullptr;
-        uint32_t *d_rec = nullptr, *used = nullptr, *sl3 = nullptr, *nsel = nullptr, *rseg = nullptr;
-        uint32_t *kA = nullptr, *vA = nullptr, *kB = nullptr, *vB = nullptr, *wcnt = nullptr, *lastid = nullptr;
+        uint32_t *d_rec = nullptr, *rseg = nullptr, *lastid = nullptr;
+        FlowKeyBuf kb;
         SegItem *big = nullptr;
         uint8_t *d_keys = nullptr;
         // histogram grouping: few flows (a table of <= HIST_MAX slots and at
@@ -830,12 +900,6 @@ extern "C" int qk_u32_encode_flows_device(qk_ctx *ctx, const uint8_t *d_bufs, si
                                                                                   (n_eff + 4095) / 4096));
         const uint64_t hchunk = ((n_eff + hnwg - 1) / hnwg + 3) & ~(uint64_t)3;   // a multiple of 4 (16-byte reads)
         uint32_t *hcnt = nullptr, *hpre = nullptr, *htot = nullptr, *hspre = nullptr, *hlast = nullptr;
-        // the occupied-slot compaction (unb workgroups of uchunk slots) and
-        // the flow-key sort's scan scratch (the side stream's own)
-        const uint32_t unb = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(1024, (C + 4095) / 4096));
-        const uint64_t uchunk = ((C + unb - 1) / unb + 255) & ~(uint64_t)255;
-        const uint32_t ks_nwg = rs_plan(ctx, nf, RS_WGPC_MAX).nwg;
-        RsScratch krs{};
         auto layout1 = [&](Carve &c) {
             if (hist) {
                 hcnt = c.take<uint32_t>((size_t)C * hnwg);
@@ -852,15 +916,9 @@ extern "C" int qk_u32_encode_flows_device(qk_ctx *ctx, const uint8_t *d_bufs, si
             d_rec = dev_out ? (uint32_t *)sketches : (uint32_t *)c.take<uint8_t>((size_t)nf * rec);
             d_keys = dev_out ? (uint8_t *)keys : c.take<uint8_t>((size_t)nf * 12);
             d_offs = c.take<uint64_t>((size_t)nf + 1);
-            // (key word, slot) arrays of the flow-key sort, taken in this order:
-            // each key array followed by its value array holds nf pairs (radix.h)
-            kA = c.take<uint32_t>(nf); vA = c.take<uint32_t>(nf); kB = c.take<uint32_t>(nf); vB = c.take<uint32_t>(nf);
-            used = c.take<uint32_t>(nf); sl3 = c.take<uint32_t>(nf);
+            kb.take(c, ctx, C, nf);   // nsel: [0] selected slots, [1] flows needing work items
             rseg = c.take<uint32_t>(nf);
-            nsel = c.take<uint32_t>(2);   // [0] selected slots, [1] flows needing work items
             big = c.take<SegItem>(nf);
-            wcnt = c.take<uint32_t>(unb);
-            krs.take(c, ks_nwg, nf);
         };
         {
             Carve probe{nullptr};
@@ -871,6 +929,8 @@ extern "C" int qk_u32_encode_flows_device(qk_ctx *ctx, const uint8_t *d_bufs, si
             Carve cv{(char *)ctx->d_flow[1]};
             layout1(cv);
         }
+        FlowSlot *const tab = ff.tab;
+        uint32_t *const rank_of_slot = ff.rank_of_slot, *const used = kb.used, *const nsel = kb.nsel;
         const uint32_t fblocks = (nf + 255) / 256;
         const uint32_t gb = (uint32_t)std::min<uint64_t>((n_eff + 255) / 256, (uint64_t)ctx->num_cus * 8);
         // Two branches (sidekick_multi.rs:265's map iteration order, and the
@@ -902,29 +962,8 @@ extern "C" int qk_u32_encode_flows_device(qk_ctx *ctx, const uint8_t *d_bufs, si
         if (!rc && hipStreamWaitEvent(s2, ctx->flow_ev[0], 0) != hipSuccess)   // (recorded behind the last extract)
             rc = QK_E_HIP;
         auto side = [&]() -> int {
-            // the occupied slots in slot order
-            hipLaunchKernelGGL(k_used_count, dim3(unb), dim3(256), 0, s2, tab, C, uchunk, wcnt);
-            hipLaunchKernelGGL(k_used_write, dim3(unb), dim3(256), 0, s2, tab, C, uchunk, wcnt, used, nsel);
-            if (hipGetLastError() != hipSuccess) return QK_E_HIP;
-            // ... in AddrKey order: one workgroup's rank sort for few flows,
-            // else an LSD radix sort of (key word, slot) pairs over the key's
-            // three 32-bit words (the next word gathered through the slots)
-            const uint32_t *sorted = sl3;
-            if (nf <= KR_MAX) {
-                hipLaunchKernelGGL(k_key_rank_small, dim3(1), dim3(1024), 0, s2, tab, used, nf, sl3);
-                if (hipGetLastError() != hipSuccess) return QK_E_HIP;
-            } else {
-                for (int q = 0; q < 3; ++q) {
-                    hipLaunchKernelGGL(k_slot_word, dim3(fblocks), dim3(256), 0, s2, tab, q ? vA : used, nf, q, kA,
-                                       q ? (uint32_t *)nullptr : vA);
-                    if (hipGetLastError() != hipSuccess) return QK_E_HIP;
-                    int where = 1;
-                    if (int e = rs_sort_k<256, 16, RS_WGPC_MAX>(ctx, kA, vA, kB, vB, nf, 32, krs, s2, where))
-                        return e;
-                    if (where != 0) return QK_E_HIP;   // four passes: the result is back in (kA, vA)
-                }
-                sorted = vA;
-            }
+            const uint32_t *sorted = nullptr;
+            if (int e = flow_key_order(ctx, s2, ff, nf, kb, &sorted)) return e;
             if (by_slot || hist) {
                 hipLaunchKernelGGL(k_slot_pos, dim3(fblocks), dim3(256), 0, s2, used, nf, rank_of_slot);
                 hipLaunchKernelGGL(k_rank_perm, dim3(fblocks), dim3(256), 0, s2, tab, sorted, nf, rank_of_slot, rseg,

@@ -35,6 +35,7 @@
 
 #include "ctx.h"
 #include "field.h"
+#include "flowjoin.h"
 #include "segments.h"
 
 namespace qk {
@@ -44,16 +45,9 @@ QK_WARM_KERNEL(flowtable)
 static_assert(sizeof(qk_u32) == 16 && sizeof(qk_flow_key) == 12, "record header 4 words, key 3 words");
 
 constexpr int FT_BLOCK = 256;
-constexpr uint32_t FT_TILE = QK_FLOW_JOIN_TILE;
-constexpr uint32_t FT_SLOTS = FT_TILE + 1;                            // the moved cut adds one key
+// (FT_TILE, FT_SLOTS, FT_CPT, FT_CHUNK, FT_NONE, the res[] words: flowjoin.h)
 constexpr uint32_t FT_IPT = (FT_SLOTS + FT_BLOCK - 1) / FT_BLOCK;     // merged positions per thread
-constexpr uint32_t FT_CPT = 4;                                        // move chunks per tile
-constexpr uint32_t FT_CHUNK = (FT_SLOTS + FT_CPT - 1) / FT_CPT;       // slots per move chunk
-constexpr uint32_t FT_NONE = 0xFFFFFFFFu;
 static_assert(FT_SLOTS * 12 <= 24 * 1024 + 12, "the staged keys take 24 KB of LDS");
-// res[] words (device, zeroed per call; copied to the pinned ctx->h_flow)
-enum { FT_TOTAL = 0, FT_MATCH = 1, FT_FLAGS = 2, FT_RES_WORDS = 4 };
-enum : unsigned long long { FT_F_ORDER = 1, FT_F_MISMATCH = 2 };
 
 // a key as three big-endian words: comparing them most significant first is
 // memcmp on the 12 bytes
@@ -404,13 +398,8 @@ static bool ft_vec(uint32_t T, const void *a, const void *b, const void *o) {
     return T % 4 == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)o) & 15) == 0;
 }
 
-// scratch of the join, carved from ctx->d_scratch
-struct FtBuf {
-    uint32_t *sa = nullptr, *sb = nullptr, *tilecnt = nullptr;
-    uint64_t *tilebase = nullptr;
-    unsigned long long *res = nullptr;
-};
-static void ft_carve(Carve &cv, FtBuf &b, size_t ntiles, size_t na, bool diff) {
+// scratch of the join, carved from ctx->d_scratch (FtBuf: flowjoin.h)
+void ft_carve(Carve &cv, FtBuf &b, size_t ntiles, size_t na, bool diff) {
     b.res = cv.take<unsigned long long>(FT_RES_WORDS);
     if (diff) {
         b.sb = cv.take<uint32_t>(na);
@@ -422,11 +411,21 @@ static void ft_carve(Carve &cv, FtBuf &b, size_t ntiles, size_t na, bool diff) {
     }
 }
 // res[] into the pinned words, after everything enqueued on s
-static int ft_read_res(qk_ctx *ctx, const FtBuf &b, hipStream_t s, uint64_t *out) {
+int ft_read_res(qk_ctx *ctx, const FtBuf &b, hipStream_t s, uint64_t *out) {
     QK_HIP_TRY(hipMemcpyAsync(ctx->h_flow, b.res, FT_RES_WORDS * 8, hipMemcpyDeviceToHost, s));
     QK_HIP_TRY(hipStreamSynchronize(s));
     std::copy(ctx->h_flow, ctx->h_flow + FT_RES_WORDS, out);
     return QK_OK;
+}
+
+int ft_join_merge(qk_ctx *ctx, hipStream_t s, const uint32_t *ka, uint32_t na, const uint32_t *kb, uint32_t nb,
+                  const FtBuf &b, size_t ntiles, uint64_t *res) {
+    QK_HIP_TRY(hipMemsetAsync(b.res, 0, FT_RES_WORDS * 8, s));
+    hipLaunchKernelGGL((k_ft_join<false>), dim3((uint32_t)ntiles), dim3(FT_BLOCK), 0, s, ka, na, kb, nb, b.sa, b.sb,
+                       b.tilecnt, b.res);
+    hipLaunchKernelGGL(k_ft_scan, dim3(1), dim3(FT_SCAN), 0, s, b.tilecnt, (uint32_t)ntiles, b.tilebase, b.res);
+    if (hipGetLastError() != hipSuccess) return QK_E_HIP;
+    return ft_read_res(ctx, b, s, res);
 }
 
 } // namespace qk
@@ -473,16 +472,9 @@ extern "C" int qk_u32_flows_merge_device(qk_ctx *ctx, const qk_flow_key *d_keys_
     const uint32_t *ka = (const uint32_t *)d_keys_a, *kb = (const uint32_t *)d_keys_b;
     int rc = QK_OK;
     uint64_t res[FT_RES_WORDS] = {0, 0, 0, 0};
-    if (hipMemsetAsync(b.res, 0, FT_RES_WORDS * 8, s) != hipSuccess) rc = QK_E_HIP;
-    if (!rc) {
-        hipLaunchKernelGGL((k_ft_join<false>), dim3((uint32_t)ntiles), dim3(FT_BLOCK), 0, s, ka, (uint32_t)na, kb,
-                           (uint32_t)nb, b.sa, b.sb, b.tilecnt, b.res);
-        hipLaunchKernelGGL(k_ft_scan, dim3(1), dim3(FT_SCAN), 0, s, b.tilecnt, (uint32_t)ntiles, b.tilebase, b.res);
-        if (hipGetLastError() != hipSuccess) rc = QK_E_HIP;
-    }
     // the one place the union's size is known: QK_E_CAPACITY (and input out of
     // order) is decided here, before anything is written to the outputs
-    if (!rc) rc = ft_read_res(ctx, b, s, res);
+    rc = ft_join_merge(ctx, s, ka, (uint32_t)na, kb, (uint32_t)nb, b, ntiles, res);
     if (!rc && (res[FT_FLAGS] & FT_F_ORDER)) rc = QK_E_INVAL;
     if (!rc) {
         *n_out = (size_t)res[FT_TOTAL];

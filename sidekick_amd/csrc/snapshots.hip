@@ -37,6 +37,7 @@
 #include "field.h"
 #include "segments.h"
 #include "snapshots.h"
+#include "snapwalk.h"
 
 namespace qk {
 
@@ -55,12 +56,6 @@ __global__ __launch_bounds__(SN_BLOCK) void k_sn_base(const uint32_t *__restrict
     if (b[0] != T) cnt[nseg] = 1;   // the host put 0 there
 }
 
-struct SnOut {
-    uint32_t *snap, *seg;
-    uint64_t *pos;
-    uint32_t *arr, *fin;
-};
-
 // the final record of flow g, which holds ids: header by one lane
 __device__ __forceinline__ void sn_final_header(uint32_t *fin, uint32_t T, uint32_t count, uint32_t last) {
     fin[0] = T;
@@ -69,16 +64,19 @@ __device__ __forceinline__ void sn_final_header(uint32_t *fin, uint32_t T, uint3
     fin[3] = last;
 }
 
-template <uint32_t KC>
-__global__ __launch_bounds__(64) void k_sn_walk(const uint32_t *__restrict__ base, const uint32_t *__restrict__ ids,
-                                                const uint32_t *__restrict__ arrival,
-                                                const uint64_t *__restrict__ offs,
-                                                const uint64_t *__restrict__ snoff, const uint32_t *__restrict__ g0s,
-                                                uint32_t nseg, uint32_t T, uint32_t f, SnOut o,
-                                                uint32_t *__restrict__ carry, uint32_t *__restrict__ part) {
+// DEST: the rows go where o.dest sends them, with key and packet index (the
+// packet path); else by flow, with seg, pos and arrival: the by-flow form is
+// compiled without any of the other's loads and tests
+template <uint32_t KC, bool DEST>
+__device__ __forceinline__ void sn_walk_body(const uint32_t *__restrict__ base, const uint32_t *__restrict__ ids,
+                                             const uint32_t *__restrict__ arrival, const uint64_t *__restrict__ offs,
+                                             const uint64_t *__restrict__ snoff, const uint32_t *__restrict__ g0s,
+                                             uint32_t nseg, uint32_t T, uint32_t f, const SnOut &o,
+                                             uint32_t *__restrict__ carry, uint32_t *__restrict__ part) {
     constexpr uint32_t LD = KC + 1;   // odd: lane = id writes its row without bank conflicts
     __shared__ uint32_t tile[64 * LD];
     __shared__ uint32_t raw[64];
+    __shared__ uint32_t l_dest[DEST ? 64 : 1], l_arr[DEST ? 64 : 1];
     const uint32_t lane = threadIdx.x, item = blockIdx.x;
     const size_t W = 4 + (size_t)T;
     const uint64_t lo = offs[0] + (uint64_t)item * SN_ITEM, end = offs[nseg];
@@ -103,6 +101,11 @@ __global__ __launch_bounds__(64) void k_sn_walk(const uint32_t *__restrict__ bas
             uint32_t pw = k0 ? pow32(x, k0) : 1u;
             __syncthreads();   // the tile before this one has been read
             raw[lane] = id;
+            // what a cut needs besides the sums, loaded with the tile (a load at the cut would stall the walk)
+            if constexpr (DEST) {
+                l_dest[lane] = lane < nt ? o.dest[tb + lane] : 0u;
+                if (k0 == 0) l_arr[lane] = lane < nt ? arrival[tb + lane] : 0u;
+            }
 #pragma unroll 4
             for (uint32_t j = 0; j < nk; ++j) {
                 pw = mul32_lazy(pw, x);
@@ -142,7 +145,9 @@ __global__ __launch_bounds__(64) void k_sn_walk(const uint32_t *__restrict__ bas
                 }
                 if (act) run = add32(run, tile[l * LD + lane]);
                 if (pos == cut) {
-                    const uint64_t row = snoff[g] + r;
+                    uint64_t row;
+                    if constexpr (DEST) row = l_dest[l];
+                    else row = snoff[g] + r;
                     if (act) o.snap[row * W + 4 + col] = run;
                     if (head) {
                         uint32_t *h = o.snap + row * W;
@@ -150,10 +155,16 @@ __global__ __launch_bounds__(64) void k_sn_walk(const uint32_t *__restrict__ bas
                         h[1] = c0 + (uint32_t)(pos - fb) + 1u;   // wrapping
                         h[2] = 1u;
                         h[3] = raw[l];
-                        o.seg[row] = g;
-                        o.pos[row] = pos;
-                        if (o.arr) o.arr[row] = arrival[pos];
+                        if constexpr (DEST) {
+                            o.arr[row] = l_arr[l];
+                        } else {
+                            o.seg[row] = g;
+                            o.pos[row] = pos;
+                            if (o.arr) o.arr[row] = arrival[pos];
+                        }
                     }
+                    if constexpr (DEST)
+                        if (k0 == 0 && lane < 3) o.key_out[row * 3 + lane] = o.keys[(size_t)g * 3 + lane];
                     ++r;
                     cut = fb + sn_cut_pos(c0, f, r);
                 }
@@ -176,6 +187,27 @@ __global__ __launch_bounds__(64) void k_sn_walk(const uint32_t *__restrict__ bas
     }
 }
 
+template <uint32_t KC>
+__global__ __launch_bounds__(64) void k_sn_walk(const uint32_t *__restrict__ base, const uint32_t *__restrict__ ids,
+                                                const uint32_t *__restrict__ arrival,
+                                                const uint64_t *__restrict__ offs,
+                                                const uint64_t *__restrict__ snoff, const uint32_t *__restrict__ g0s,
+                                                uint32_t nseg, uint32_t T, uint32_t f, SnOut o,
+                                                uint32_t *__restrict__ carry, uint32_t *__restrict__ part) {
+    sn_walk_body<KC, false>(base, ids, arrival, offs, snoff, g0s, nseg, T, f, o, carry, part);
+}
+template <uint32_t KC>
+__global__ __launch_bounds__(64) void k_sn_walk_dest(const uint32_t *__restrict__ base,
+                                                     const uint32_t *__restrict__ ids,
+                                                     const uint32_t *__restrict__ arrival,
+                                                     const uint64_t *__restrict__ offs,
+                                                     const uint64_t *__restrict__ snoff,
+                                                     const uint32_t *__restrict__ g0s, uint32_t nseg, uint32_t T,
+                                                     uint32_t f, SnOut o, uint32_t *__restrict__ carry,
+                                                     uint32_t *__restrict__ part) {
+    sn_walk_body<KC, true>(base, ids, arrival, offs, snoff, g0s, nseg, T, f, o, carry, part);
+}
+
 __global__ __launch_bounds__(SN_BLOCK) void k_sn_chain(const SnChain *__restrict__ chains, uint32_t T,
                                                        uint32_t *__restrict__ carry,
                                                        const uint32_t *__restrict__ part) {
@@ -192,12 +224,13 @@ __global__ __launch_bounds__(SN_BLOCK) void k_sn_chain(const SnChain *__restrict
 // item = blockIdx.x + 1 (the first item has no flow from before)
 __global__ __launch_bounds__(SN_BLOCK) void k_sn_carry(const uint32_t *__restrict__ base,
                                                        const uint32_t *__restrict__ ids,
+                                                       const uint32_t *__restrict__ arrival,
                                                        const uint64_t *__restrict__ offs,
                                                        const uint64_t *__restrict__ snoff,
                                                        const uint32_t *__restrict__ g0s, uint32_t nseg, uint32_t T,
-                                                       uint32_t f, uint32_t *__restrict__ snap,
-                                                       uint32_t *__restrict__ fin, const uint32_t *__restrict__ carry,
+                                                       uint32_t f, SnOut o, const uint32_t *__restrict__ carry,
                                                        const uint32_t *__restrict__ part) {
+    uint32_t *__restrict__ snap = o.snap, *__restrict__ fin = o.fin;
     const uint32_t item = blockIdx.x + 1;
     const size_t W = 4 + (size_t)T;
     const uint64_t lo = offs[0] + (uint64_t)item * SN_ITEM, end = offs[nseg];
@@ -207,7 +240,11 @@ __global__ __launch_bounds__(SN_BLOCK) void k_sn_carry(const uint32_t *__restric
     if (fb >= lo) return;
     const uint64_t e = fe < hi ? fe : hi;
     const uint32_t c0 = base[g * W + 1];
-    const uint64_t r0 = snoff[g] + sn_ncuts(c0, f, lo - fb);
+    const uint64_t r0 = sn_ncuts(c0, f, lo - fb);   // the flow's cuts in front of the item
+    // (the cut's position only where dest needs it: by flow the row is plain arithmetic, as it was)
+    auto at = [&](uint32_t row) -> uint64_t {
+        return o.dest ? (uint64_t)o.dest[fb + sn_cut_pos(c0, f, r0 + row)] : snoff[g] + r0 + row;
+    };
     const uint32_t nrows = (uint32_t)(sn_ncuts(c0, f, e - fb) - sn_ncuts(c0, f, lo - fb));   // <= SN_ITEM
     const uint32_t *cin = carry + (size_t)item * T;
     if (T <= SN_BLOCK) {
@@ -216,7 +253,7 @@ __global__ __launch_bounds__(SN_BLOCK) void k_sn_carry(const uint32_t *__restric
         if (sub < per) {
             const uint32_t c = cin[col];
             for (uint32_t row = sub; row < nrows; row += per) {
-                uint32_t *p = snap + (r0 + row) * W + 4 + col;
+                uint32_t *p = snap + at(row) * W + 4 + col;
                 *p = add32(*p, c);
             }
         }
@@ -224,7 +261,7 @@ __global__ __launch_bounds__(SN_BLOCK) void k_sn_carry(const uint32_t *__restric
         for (uint32_t col = threadIdx.x; col < T; col += SN_BLOCK) {
             const uint32_t c = cin[col];
             for (uint32_t row = 0; row < nrows; ++row) {
-                uint32_t *p = snap + (r0 + row) * W + 4 + col;
+                uint32_t *p = snap + at(row) * W + 4 + col;
                 *p = add32(*p, c);
             }
         }
@@ -294,30 +331,19 @@ extern "C" int qk_u32_snapshot_segments_device(qk_ctx *ctx, const uint8_t *d_bas
     }
     hipStream_t s = pick_stream(ctx, stream);
 
-    // pinned: the counts and the flag, then the items' first flows and the
-    // chains (their number bounded by the offsets alone, so the buffer never
-    // moves under the copy)
+    // pinned: the counts and the flag, then (sn_walk_run) the items' first
+    // flows and the chains — their number bounded by the offsets alone, so the
+    // buffer never moves under the copy
     const size_t cnt_bytes = (((nseg + 1) * sizeof(uint32_t)) + 15) & ~(size_t)15;
-    const size_t g0_bytes = ((ni * sizeof(uint32_t)) + 15) & ~(size_t)15;
-    const size_t chain_cap = std::min(nseg, ni);
-    if (int e = ensure_items(ctx, cnt_bytes + g0_bytes + chain_cap * sizeof(SnChain) + 16)) return e;
+    if (int e = ensure_items(ctx, cnt_bytes + sn_pinned_bytes(nseg, ni))) return e;
     uint32_t *h_cnt = (uint32_t *)ctx->h_items;
-    uint32_t *h_g0 = (uint32_t *)((char *)ctx->h_items + cnt_bytes);
-    SnChain *h_chain = (SnChain *)((char *)ctx->h_items + cnt_bytes + g0_bytes);
-    const uint32_t *d_g0 = (const uint32_t *)((const char *)ctx->h_items_dev + cnt_bytes);
-    const SnChain *d_chain = (const SnChain *)((const char *)ctx->h_items_dev + cnt_bytes + g0_bytes);
 
-    uint32_t *d_cnt = nullptr, *d_carry = nullptr, *d_part = nullptr;
-    uint64_t *d_offs = nullptr, *d_snoff = nullptr;
+    uint32_t *d_cnt = nullptr;
     for (int pass = 0; pass < 2; ++pass) {
         Carve cv{pass ? (char *)ctx->d_flow[1] : nullptr};
         d_cnt = cv.take<uint32_t>(nseg + 1);
-        d_offs = cv.take<uint64_t>(nseg + 1);
-        d_snoff = cv.take<uint64_t>(nseg + 1);
-        d_carry = cv.take<uint32_t>((ni + 1) * T);
-        d_part = cv.take<uint32_t>(ni * T);
         if (!pass)
-            if (int e = ensure_flow(ctx, 1, cv.off, s)) return e;
+            if (int e = ensure_flow(ctx, 1, cv.off + sn_arena_bytes(nseg, ni, T), s)) return e;
     }
     const uint32_t *base = (const uint32_t *)d_base;
     const uint32_t seg_blocks = (uint32_t)((nseg + SN_BLOCK - 1) / SN_BLOCK);
@@ -339,14 +365,64 @@ extern "C" int qk_u32_snapshot_segments_device(qk_ctx *ctx, const uint8_t *d_bas
     if (total > cap) return QK_E_CAPACITY;
     if (!n && !d_final_out) return QK_OK;
 
+    SnOut o{};
+    o.snap = (uint32_t *)d_snap_out, o.seg = d_snap_seg_out, o.pos = d_snap_pos_out, o.arr = d_snap_arrival_out;
+    o.fin = (uint32_t *)d_final_out;
+    return sn_walk_run(ctx, s, base, d_ids, d_arrival, offsets, snap_offsets, nseg, T, f, o, cnt_bytes);
+}
+
+// bytes of pinned memory and of arena 1 that sn_walk_run takes
+size_t qk::sn_pinned_bytes(size_t nseg, size_t ni) {
+    return ((ni * sizeof(uint32_t) + 15) & ~(size_t)15) + std::min(nseg, ni) * sizeof(SnChain) + 16;
+}
+size_t qk::sn_arena_bytes(size_t nseg, size_t ni, uint32_t T) {
+    Carve cv{nullptr};
+    cv.take<uint64_t>(nseg + 1);
+    cv.take<uint64_t>(nseg + 1);
+    cv.take<uint32_t>((ni + 1) * T);
+    cv.take<uint32_t>(ni * T);
+    return cv.off + 256;
+}
+
+int qk::sn_walk_run(qk_ctx *ctx, hipStream_t s, const uint32_t *base, const uint32_t *d_ids, const uint32_t *d_arrival,
+                    const uint64_t *offsets, const uint64_t *snap_offsets, size_t nseg, uint32_t T, uint32_t f,
+                    const SnOut &o, size_t pinned_off) {
+    const size_t W = 4 + (size_t)T;
+    const size_t ni = sn_items(offsets, nseg);
+    const size_t g0_bytes = ((ni * sizeof(uint32_t)) + 15) & ~(size_t)15;
+    if (int e = ensure_items(ctx, pinned_off + sn_pinned_bytes(nseg, ni))) return e;
+    uint32_t *h_g0 = (uint32_t *)((char *)ctx->h_items + pinned_off);
+    SnChain *h_chain = (SnChain *)((char *)ctx->h_items + pinned_off + g0_bytes);
+    const uint32_t *d_g0 = (const uint32_t *)((const char *)ctx->h_items_dev + pinned_off);
+    const SnChain *d_chain = (const SnChain *)((const char *)ctx->h_items_dev + pinned_off + g0_bytes);
+    // arena 1, from its end: the caller's own use of it comes first
+    if (ctx->flow_bytes[1] < sn_arena_bytes(nseg, ni, T)) return QK_E_HIP;
+    uint32_t *d_carry = nullptr, *d_part = nullptr;
+    uint64_t *d_offs = nullptr, *d_snoff = nullptr;
+    {
+        // rounded up: never below the caller's own bytes (sn_arena_bytes holds 256 bytes of slack for it)
+        const size_t at = (ctx->flow_bytes[1] - sn_arena_bytes(nseg, ni, T) + 255) & ~(size_t)255;
+        Carve cv{(char *)ctx->d_flow[1] + at};
+        d_offs = cv.take<uint64_t>(nseg + 1);
+        d_snoff = cv.take<uint64_t>(nseg + 1);
+        d_carry = cv.take<uint32_t>((ni + 1) * T);
+        d_part = cv.take<uint32_t>(ni * T);
+    }
+    if (o.dest && (!d_arrival || !o.arr || !o.keys || !o.key_out)) return QK_E_INVAL;   // the packet form writes all of them
+    int rc = QK_OK;
     const size_t nc = ni ? sn_plan_items(offsets, nseg, h_g0, h_chain) : 0;
     if (hipMemcpyAsync(d_offs, offsets, (nseg + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
         hipMemcpyAsync(d_snoff, snap_offsets, (nseg + 1) * 8, hipMemcpyHostToDevice, s) != hipSuccess)
         rc = QK_E_HIP;
-    uint32_t *fin = (uint32_t *)d_final_out;
+    uint32_t *fin = o.fin;
     if (!rc && ni) {
-        const SnOut o{(uint32_t *)d_snap_out, d_snap_seg_out, d_snap_pos_out, d_snap_arrival_out, fin};
-        if (T <= SN_KC_SMALL)
+        if (o.dest && T <= SN_KC_SMALL)
+            hipLaunchKernelGGL(k_sn_walk_dest<SN_KC_SMALL>, dim3((uint32_t)ni), dim3(64), 0, s, base, d_ids, d_arrival,
+                               d_offs, d_snoff, d_g0, (uint32_t)nseg, T, f, o, d_carry, d_part);
+        else if (o.dest)
+            hipLaunchKernelGGL(k_sn_walk_dest<SN_KC>, dim3((uint32_t)ni), dim3(64), 0, s, base, d_ids, d_arrival, d_offs,
+                               d_snoff, d_g0, (uint32_t)nseg, T, f, o, d_carry, d_part);
+        else if (T <= SN_KC_SMALL)
             hipLaunchKernelGGL((k_sn_walk<SN_KC_SMALL>), dim3((uint32_t)ni), dim3(64), 0, s, base, d_ids, d_arrival,
                                d_offs, d_snoff, d_g0, (uint32_t)nseg, T, f, o, d_carry, d_part);
         else
@@ -359,8 +435,8 @@ extern "C" int qk_u32_snapshot_segments_device(qk_ctx *ctx, const uint8_t *d_bas
         if (hipGetLastError() != hipSuccess) rc = QK_E_HIP;
     }
     if (!rc && ni > 1) {
-        hipLaunchKernelGGL(k_sn_carry, dim3((uint32_t)(ni - 1)), dim3(SN_BLOCK), 0, s, base, d_ids, d_offs, d_snoff,
-                           d_g0, (uint32_t)nseg, T, f, (uint32_t *)d_snap_out, fin, d_carry, d_part);
+        hipLaunchKernelGGL(k_sn_carry, dim3((uint32_t)(ni - 1)), dim3(SN_BLOCK), 0, s, base, d_ids, d_arrival, d_offs,
+                           d_snoff, d_g0, (uint32_t)nseg, T, f, o, d_carry, d_part);
         if (hipGetLastError() != hipSuccess) rc = QK_E_HIP;
     }
     if (!rc && fin) {

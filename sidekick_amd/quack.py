@@ -34,6 +34,9 @@ plus the batch entry points of the MI355X engine:
                              count to a multiple of frequency_pkts, for a batch.
     DeviceFlowSnapshots      the proxy's table by flow index: a batch in, the
                              datagrams of sidekick_multi.rs:271-283 out, in order.
+    snapshot_flows(..)       the same from captured packets against the table
+                             held by AddrKey: filter, key, Resets, every
+                             crossing in send order, the table after the batch.
     flows_merge / flows_diff / flows_lookup, DeviceFlowQuacks
                              SidekickMulti's flow table as key-sorted arrays in
                              HBM: merge a batch, diff against a peer, look up.
@@ -65,7 +68,7 @@ __all__ = [
     "arithmetic", "Context", "get_context", "device_count", "FlowQuacks",
     "to_coeffs_segments", "decode_segments", "sender_step", "drain_segments", "SenderStep",
     "update_segments", "DeviceSenderLog", "SenderLogStep", "sender_steps", "SenderSteps",
-    "snapshot_segments", "Snapshots", "DeviceFlowSnapshots",
+    "snapshot_segments", "Snapshots", "DeviceFlowSnapshots", "snapshot_flows", "FlowSnapshots",
     "flows_merge", "flows_diff", "flows_lookup", "DeviceFlowQuacks",
     "emit_wire", "ingest_wire", "ingest_wire_queue", "wire_max",
 ]
@@ -1405,6 +1408,75 @@ def ingest_wire_queue(wire, lens, flow, nflows: int, threshold: int, ctx: Contex
     return queue[:m], q_offsets, status[:n], m
 
 
+@dataclass
+class FlowSnapshots:
+    """What snapshot_flows returns: the m quACKs the proxy loop sends for a
+    batch of captures, in send order, and the flow table after the batch."""
+    records: object          # CUDA int32 [m, 4 + t]: the quACK after each emitting packet
+    keys: object             # CUDA uint8 [m, 12]: its flow's AddrKey
+    index: object            # CUDA int32 [m]: the packet's index in the batch, ascending
+    table_keys: object       # CUDA uint8 [nt, 12]: the table after the last packet, keys ascending
+    table_sketches: object   # CUDA int32 [nt, 4 + t]
+    stats: dict              # qk_pkt_stats, as encode_flows gives them
+
+
+def snapshot_flows(bufs, threshold: int, frequency_pkts: int, keys=None, sketches=None, stride: int = 67, meta=None,
+                   my_addr=None, ctx: Context | None = None, table_out=None, snap_cap: int | None = None
+                   ) -> FlowSnapshots:
+    """start_sidekick_multi_frequency_pkts over a batch of captured records
+    (sidekick_multi.rs:240-287) on the device (qk_u32_snapshot_flows_device):
+    every packet is filtered and keyed as encode_flows does, an Insert goes into
+    its flow's quACK of the table `keys` / `sketches` (a flow array as
+    encode_flows(device_out=True) returns it; None: an empty table), a Reset
+    empties the table, and every packet that brings its flow's count to a
+    multiple of `frequency_pkts` emits that quACK.  Returns the emitted quACKs
+    in the reference's send order (Resets inside the batch honoured: those sent
+    before one are included) and the table after the last packet.
+    `table_out`: a (keys, sketches) pair of tensors to write the table into
+    (DeviceFlowQuacks' spare buffer) when they hold enough rows; `snap_cap`: the
+    snapshot rows first allocated (a batch of more runs a second time with the
+    sizes the first run reports)."""
+    ctx = _context(ctx, bufs, sketches)
+    n, dev, mptr = packet_batch(bufs, stride, meta)
+    torch = need_torch()
+    t, f = int(threshold), int(frequency_pkts)
+    if not 0 <= f < 1 << 32:
+        raise ValueError("frequency_pkts must fit a u32")
+    nt = 0
+    if keys is not None or sketches is not None:
+        nt, tt = _flow_array(keys, sketches, "table")
+        if tt != t:
+            raise QuackError(QK_E_MISMATCH, "snapshot_flows: the table's threshold differs")
+    device, W = bufs.device, 4 + t
+    addr = (C.c_uint8 * 6)(*my_addr) if my_addr is not None else None
+    stream = stream_of(bufs)
+    # one snapshot per frequency_pkts packets and one per flow for its phase, if every packet were an Insert
+    if snap_cap is None:
+        snap_cap = min(n, n // max(f, 1) + nt + 1024)
+
+    def attempt(caps):
+        tcap, scap = caps
+        if table_out is not None and table_out[0].shape[0] >= tcap:
+            ko, so = table_out[0], table_out[1]
+            tcap = ko.shape[0]
+        else:
+            ko = torch.empty((max(tcap, 1), 12), dtype=torch.uint8, device=device)
+            so = torch.empty((max(tcap, 1), W), dtype=torch.int32, device=device)
+        rec = torch.empty((max(scap, 1), W), dtype=torch.int32, device=device)
+        sk_ = torch.empty((max(scap, 1), 12), dtype=torch.uint8, device=device)
+        si = torch.empty((max(scap, 1),), dtype=torch.int32, device=device)
+        ntab, m, st = C.c_size_t(), C.c_size_t(), PktStats()
+        rc = lib().qk_u32_snapshot_flows_device(
+            ctx.handle, bufs.data_ptr() if n else None, n, stride, mptr, addr, t, f,
+            keys.data_ptr() if nt else None, sketches.data_ptr() if nt else None, nt,
+            ko.data_ptr(), so.data_ptr(), tcap, C.byref(ntab), rec.data_ptr(), sk_.data_ptr(), si.data_ptr(), scap,
+            C.byref(m), C.byref(st), stream)
+        return rc, (max(ntab.value, tcap), max(m.value, scap)), (ko, so, ntab.value, rec, sk_, si, m.value, st)
+    ko, so, ntab, rec, sk_, si, m, st = retry_capacity(attempt, (nt + min(n, 1024), int(snap_cap)), "snapshot_flows")
+    stats = {k: getattr(st, k) for k, _ in PktStats._fields_}
+    return FlowSnapshots(rec[:m], sk_[:m], si[:m], ko[:ntab], so[:ntab], stats)
+
+
 class DeviceFlowQuacks:
     """SidekickMulti's flow table (sidekick_multi.rs:36,65-90) resident in HBM:
     FlowQuacks' surface over a key-sorted flow array.  A batch goes
@@ -1469,7 +1541,7 @@ class DeviceFlowQuacks:
         return emit_wire(self.keys, self.sketches, select, stride, ctx)
 
     def insert_packets(self, bufs, stride: int = 67, meta=None, my_addr=None, frequency_pkts: int = 0,
-                       ctx: Context | None = None, emit: bool = False) -> dict:
+                       ctx: Context | None = None, emit: bool = False, every: bool = False) -> dict:
         """Batch of captured records (CUDA uint8 tensor): extract, group by
         AddrKey and encode per flow on the device, then merge into the table
         there.  A batch with a Reset replaces the table, as FlowQuacks does.
@@ -1479,8 +1551,15 @@ class DeviceFlowQuacks:
         to send for them is the end-of-batch one.  emit=True: the due flows'
         wire images are built on the device instead, stats["wire"] = the
         (keys, rows, wire, lens) of emit(select=due), and no key crosses to the
-        host (stats["due"] is then left empty)."""
+        host (stats["due"] is then left empty).
+        every=True: the reference's loop itself (snapshot_flows): the table is
+        updated packet by packet, Resets inside the batch included, and
+        stats["wire"] = the (keys, index, wire, lens, records) of EVERY quACK
+        the loop sends, in send order: one per crossing of frequency_pkts, not
+        one per flow and batch (index: the emitting packet's)."""
         ctx = ctx or get_context(self.device)
+        if every:
+            return self._insert_packets_every(bufs, stride, meta, my_addr, frequency_pkts, ctx)
         keys, sk, stats = encode_flows(bufs, self.threshold, stride, meta, my_addr, ctx, device_out=True,
                                        cap=self._batch_cap)
         # room for the next batch's flows: a batch of more runs twice
@@ -1494,6 +1573,28 @@ class DeviceFlowQuacks:
         elif frequency_pkts:
             hit = self.keys[due.bool()].cpu().numpy()
             stats["due"] = [hit[i].tobytes() for i in range(hit.shape[0])]
+        return stats
+
+    def _insert_packets_every(self, bufs, stride, meta, my_addr, frequency_pkts, ctx) -> dict:
+        o = 1 - self._cur
+        spare = self._bufs[o][:2] if self._bufs[o] is not None else None
+        s = snapshot_flows(bufs, self.threshold, frequency_pkts, self.keys if self._n else None,
+                           self.sketches if self._n else None, stride, meta, my_addr, ctx, table_out=spare)
+        n = s.table_keys.shape[0]
+        if spare is None or s.table_keys.data_ptr() != spare[0].data_ptr():
+            # a fresh table: room to grow, and a `due` column for merge()
+            torch, dev = need_torch(), f"cuda:{self.device}"
+            rows = max(n + n // 8, 1024)
+            self._bufs[o] = (torch.empty((rows, 12), dtype=torch.uint8, device=dev),
+                             torch.empty((rows, 4 + self.threshold), dtype=torch.int32, device=dev),
+                             torch.empty((rows,), dtype=torch.uint8, device=dev))
+            self._bufs[o][0][:n].copy_(s.table_keys)
+            self._bufs[o][1][:n].copy_(s.table_sketches)
+        self._cur, self._n = o, n
+        _, _, wire, lens = emit_wire(None, s.records, ctx=ctx)
+        stats = s.stats
+        stats["due"] = []
+        stats["wire"] = (s.keys, s.index, wire, lens, s.records)
         return stats
 
     def quacks(self, keys, ctx: Context | None = None) -> list:
